@@ -14,6 +14,14 @@ tables, occupancy bitfield) are resident in HBM when the timed region starts.
 Multi-GPU = ray data parallel, weak scaling (4096 rays per GPU), one RCCL all-reduce of the flat
 student gradient per step (only the table rows the occupancy grid lets a sample touch: 13 of 69 MB).  Rank 0 prints ONE
 JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, ms_per_step, dtype, config).
+Everything else the line can carry is measured only with --full: the sustained window, the roofline kernel's runs
+(in the step, alone, speed of light), the CPU and reference-kernel baselines, the staged PSNR run and, under ray-DP,
+the collective alone (`roofline`, `sustained`, `cpu_baseline`, `gpu_reference`, `psnr` are null without it).
+
+    python bench.py --full                                       # the whole line
+    python bench.py --steps 20 --warmup 5 --dump-outputs DIR     # + DIR/<name>.npy: what the last timed step returned
 """
 import argparse
 import json
@@ -403,6 +411,8 @@ def teacher_workload(args, dev):
                 loss, pred = tr.train_step(*batches[it % 16])
             torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # (the last timed step's; the eager steps behind a timed block write no graph output)
+        dump_outputs(args.dump_outputs, {"loss": loss, "pred": pred})
     name = max(sorted(names), key=kt.launches)
     ms = kt.mean_ms(name)
     B, D, C, L, dt_code = kt.meta[name][-1]
@@ -433,6 +443,38 @@ def teacher_workload(args, dev):
             traceback.print_exc(file=sys.stderr)
             out["cpu_baseline"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
     print(json.dumps(out))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array (None entries skipped).  An array larger than its share of 64 MB is
+    replaced by a fixed sample of its flattened elements (seeded indices, ascending), so two builds compare element for element."""
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy() if torch.is_tensor(t) else np.asarray(t, dtype=np.float32)
+        if a.size > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _emit(out, rank):
+    """Leave the process group and print the ONE line (rank 0)."""
+    if dist.is_initialized():
+        dist.destroy_process_group()
+    if rank == 0:
+        # the JSON line must be the LAST thing on stdout: the communication library writes its version banner through the C
+        # runtime's buffer, which would otherwise be flushed at exit, after Python's
+        import ctypes
+        try:
+            ctypes.CDLL(None).fflush(None)
+        except Exception:  # noqa: BLE001
+            pass
+        print(json.dumps(out), flush=True)
 
 
 def _spawn_ranks(n):
@@ -486,7 +528,14 @@ def main():
                     help="SURVEY 8(d)'s occupancy sweep: ~1 / ~5 (the metric's scene) / ~15 %% of the 128^3 cells occupied (ChairScene(thicken = 0 / 0.08 / 0.2))")
     ap.add_argument("--workload", choices=["distill", "teacher"], default="distill",
                     help="distill = BASELINE.json's metric (configs[2]); teacher = hash teacher training step (configs[1], single GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="distill: after the timed steps also run the sustained window, the roofline measurement, the CPU / reference-kernel "
+                         "baselines, the staged PSNR run and (ray-DP) the collective alone; each still obeys its own option above")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, loss terms, student / teacher images) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` started the way the driver starts `--gpus 1`: spawn the N ranks here (one process per GPU through
@@ -556,8 +605,9 @@ def main():
     def record(spg):
         """The step as HIP graph(s) of spg steps each (launch-bound eagerly: ~200 kernels of a few us); returns how it is launched."""
         try:
-            # (roofline, in_step) every recorded launch of the teacher's lookup + head leaves its own extent behind: read after the timed region
-            w.trainer.record_fused_spans = not dp.enabled
+            # (roofline, in_step; --full) every recorded launch of the teacher's lookup + head leaves its own extent behind: read after the
+            # timed region
+            w.trainer.record_fused_spans = args.full and not dp.enabled
             w.enable_graph(steps_per_graph=spg)
             return "hipGraph replay" + (" (%d steps per graph launch%s)" % (
                 w.steps_per_call, (", the next replay's marches + teacher forwards on ONE forked branch per graph" if getattr(w.trainer, "pipeline_fork", "") == "graph" else
@@ -624,6 +674,57 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+
+    samples = int(w.stu.step_counter[:, 0].float().mean().item())
+    bits = w.stu.density_bitfield
+    occupied = float(sum(int(((bits >> k) & 1).sum()) for k in range(8))) / float(bits.numel() * 8)
+    total_rays = args.steps * global_rays
+    out = {
+        "metric": "train rays/s (%s->%s chair distillation step)" % (opt.teacher_type, opt.model_type),
+        "value": total_rays / elapsed,
+        "unit": "rays/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if args.fp32 else "f16 tables+MLP (AMP, as the reference forces) / f32 marcher+compositor",
+        "data": "synthetic (analytic chair-like scene, 800x800 Blender-style cameras at r=3.2; no dataset offline)",
+        "config": {"workload": "distill %s->%s, synthetic chair, %s cameras, stage 3 (rgb + feature/sigma/colour losses), %d rays/GPU/step, "
+                               "occupancy 128^3 %.1f%% occupied, max_steps 1024, teacher pre-trained %d steps%s" % (
+                                   args.teacher, args.student, args.data_type, args.rays, 100.0 * occupied, args.teacher_pretrain,
+                                   "" if (args.bound == 1.0 and args.dt_gamma == 0.0) else "; bound %g (%d cascades), dt_gamma %g, scene scale %g"
+                                   % (args.bound, w.stu.cascade, args.dt_gamma, args.scene_scale)),
+                   "rays_per_gpu": args.rays, "parallelism": "ray-dp%d" % world, "launch": launch_mode,
+                   "update": {"late": "AdamW in two launches: rows the backward can write behind the scatter; the L1-only rows one step later on the forked "
+                                      "branch (same bits; the reported loss counts their L1 value one step late)",
+                              "1": "AdamW in two launches (L1-only rows at the start of the next step's branch)"}.get(
+                       getattr(w.trainer, "adamw_split", "0"), "AdamW in one launch"),
+                   # steps that ran before the timed window beyond --warmup (each is a real optimisation step): the three eager steps every
+                   # recording starts with, and the untimed first replay of a timed recording that the warm-up count does not divide
+                   "untimed_steps_beyond_warmup": (0 if args.eager else 3 * (2 if two_recordings else 1)) + untimed_extra,
+                   "capture_fallback": (not args.eager) and not launch_mode.startswith("hipGraph replay"),  # True = the step fell back to eager launches (~5x the ms)
+                   "samples_per_step_per_gpu": samples,
+                   # rays/s depends on the scene through the samples a ray generates: the transferable figure is samples/s (SURVEY 8d)
+                   "occupied_fraction": occupied, "samples_per_ray": samples / float(args.rays),
+                   "samples_per_s": samples * world * args.steps / elapsed,
+                   "padded_rows_per_step": int(w.stu.mean_count) + 128 - int(w.stu.mean_count) % 128,
+                   "teacher_psnr_db": w.teacher_psnr,
+                   "psnr_student_vs_teacher_db": float(psnr(pred_stu.detach(), pred_tea.detach())) if pred_stu is not None else None,
+                   "loss": float(loss)},
+        "roofline": None,
+        "sustained": None,
+        "cpu_baseline": None,
+        "gpu_reference": None,
+        "psnr": None,
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict({"loss": loss, "pred_stu": pred_stu, "pred_tea": pred_tea},
+                                             **{"loss_" + k: v for k, v in info.items()}))
+    if not args.full:
+        return _emit(out, rank)
 
     # ---- a longer window behind the timed one (the driver's K = 20 steps are 6 ms: nothing outside this process can see them)
     sustained = None
@@ -873,48 +974,7 @@ def main():
     except Exception as e:  # noqa: BLE001  (never lose the throughput line to the roofline measurement)
         roof = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
 
-    samples = int(w.stu.step_counter[:, 0].float().mean().item())
-    bits = w.stu.density_bitfield
-    occupied = float(sum(int(((bits >> k) & 1).sum()) for k in range(8))) / float(bits.numel() * 8)
-    total_rays = args.steps * global_rays
-    out = {
-        "metric": "train rays/s (%s->%s chair distillation step)" % (opt.teacher_type, opt.model_type),
-        "value": total_rays / elapsed,
-        "unit": "rays/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f32" if args.fp32 else "f16 tables+MLP (AMP, as the reference forces) / f32 marcher+compositor",
-        "data": "synthetic (analytic chair-like scene, 800x800 Blender-style cameras at r=3.2; no dataset offline)",
-        "config": {"workload": "distill %s->%s, synthetic chair, %s cameras, stage 3 (rgb + feature/sigma/colour losses), %d rays/GPU/step, "
-                               "occupancy 128^3 %.1f%% occupied, max_steps 1024, teacher pre-trained %d steps%s" % (
-                                   args.teacher, args.student, args.data_type, args.rays, 100.0 * occupied, args.teacher_pretrain,
-                                   "" if (args.bound == 1.0 and args.dt_gamma == 0.0) else "; bound %g (%d cascades), dt_gamma %g, scene scale %g"
-                                   % (args.bound, w.stu.cascade, args.dt_gamma, args.scene_scale)),
-                   "rays_per_gpu": args.rays, "parallelism": "ray-dp%d" % world, "launch": launch_mode,
-                   "update": {"late": "AdamW in two launches: rows the backward can write behind the scatter; the L1-only rows one step later on the forked "
-                                      "branch (same bits; the reported loss counts their L1 value one step late)",
-                              "1": "AdamW in two launches (L1-only rows at the start of the next step's branch)"}.get(
-                       getattr(w.trainer, "adamw_split", "0"), "AdamW in one launch"),
-                   # steps that ran before the timed window beyond --warmup (each is a real optimisation step): the three eager steps every
-                   # recording starts with, and the untimed first replay of a timed recording that the warm-up count does not divide
-                   "untimed_steps_beyond_warmup": (0 if args.eager else 3 * (2 if two_recordings else 1)) + untimed_extra,
-                   "capture_fallback": (not args.eager) and not launch_mode.startswith("hipGraph replay"),  # True = the step fell back to eager launches (~5x the ms)
-                   "samples_per_step_per_gpu": samples,
-                   # rays/s depends on the scene through the samples a ray generates: the transferable figure is samples/s (SURVEY 8d)
-                   "occupied_fraction": occupied, "samples_per_ray": samples / float(args.rays),
-                   "samples_per_s": samples * world * args.steps / elapsed,
-                   "padded_rows_per_step": int(w.stu.mean_count) + 128 - int(w.stu.mean_count) % 128,
-                   "teacher_psnr_db": w.teacher_psnr,
-                   "psnr_student_vs_teacher_db": float(psnr(pred_stu.detach(), pred_tea.detach())) if pred_stu is not None else None,
-                   "loss": float(loss)},
-        "roofline": roof,
-        "sustained": sustained,
-    }
+    out["roofline"], out["sustained"] = roof, sustained
     if dp.enabled:  # what one step's gradient exchange moved (informational; never let it cost the line)
         try:
             tr = w.trainer
@@ -973,10 +1033,6 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w, args.cpu_steps, args.rays)
         out["gpu_reference"] = gpu_reference_step(opt)
-    else:
-        out["cpu_baseline"] = None
-        out["gpu_reference"] = None
-    out["psnr"] = None
     if rank == 0 and world == 1 and not args.no_psnr and not args.eager and args.student == "vm" and args.bound == 1.0:
         try:
             del w  # (its graphs and pools)
@@ -989,17 +1045,7 @@ def main():
             import traceback
             traceback.print_exc(file=sys.stderr)
             out["psnr"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-    if dist.is_initialized():
-        dist.destroy_process_group()
-    if rank == 0:
-        # the JSON line must be the LAST thing on stdout: the communication library writes its version banner through the C
-        # runtime's buffer, which would otherwise be flushed at exit, after Python's
-        import ctypes
-        try:
-            ctypes.CDLL(None).fflush(None)
-        except Exception:  # noqa: BLE001
-            pass
-        print(json.dumps(out), flush=True)
+    _emit(out, rank)
 
 
 if __name__ == "__main__":

@@ -43,14 +43,28 @@ def test_sh_wrapper_logic_matches_reference_wrapper():
     assert np.array_equal(d.grad.numpy(), G["sh_gd"])
 
 
+def _ulps(a, b):
+    """largest distance in float32 units in the last place between paired values (each pair of one sign, as here)"""
+    return int(np.abs(a.astype(np.float32).view(np.int32).astype(np.int64) - b.astype(np.float32).view(np.int32).astype(np.int64)).max())
+
+
 def test_trunc_exp():
+    """The fixture's bits are torch.exp of the machine that wrote it, and PyTorch-CPU's float32 exp is not the same function
+    everywhere: MKL picks its vector code by CPU, and those paths disagree in the last bit (16-20 of these 401 values move by
+    1 ulp between MKL_CBWR=AVX2 / COMPATIBLE and the AVX-512 path the fixture was written on).  So the restatement is pinned
+    bit for bit to this machine's float32 exp -- forward exp(x), backward g * exp(x clamped to [-12, 12]) -- and to the
+    reference's own outputs up to the 1 ulp each side may be off from the correctly rounded value; a different clamp or
+    precision is off by far more than that."""
     from pvd.activation import make_trunc_exp
     te = make_trunc_exp("cpu")
     x = torch.from_numpy(G["te_x"]).requires_grad_(True)
+    g = torch.from_numpy(G["te_g"])
     y = te(x)
-    assert np.array_equal(y.detach().numpy(), G["te_y"])
-    y.backward(torch.from_numpy(G["te_g"]))
-    assert np.array_equal(x.grad.numpy(), G["te_gx"])
+    assert torch.equal(y.detach(), torch.exp(x.detach()))
+    assert _ulps(y.detach().numpy(), G["te_y"]) <= 2
+    y.backward(g)
+    assert torch.equal(x.grad, g * torch.exp(x.detach().clamp(-12, 12)))
+    assert _ulps(x.grad.numpy(), G["te_gx"]) <= 2
 
 
 @pytest.mark.parametrize("mr", [10, 2, 6])

@@ -1,5 +1,5 @@
-"""bench.py's contract, end to end, on the one GPU of the box: the JSON line of the single-GPU run (metric, config, roofline
-and -- when asked for -- cpu_baseline objects), and the N > 1 launch exactly as the driver issues it
+"""bench.py's contract, end to end, on the one GPU of the box: the JSON line of the single-GPU run (metric and config; with --full
+the roofline, sustained, cpu_baseline, gpu_reference and psnr objects), --dump-outputs, and the N > 1 launch exactly as the driver issues it
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 ...`) with both ranks sharing the GPU
 over gloo (PVD_DIST_BACKEND=gloo): ray-DP capture, gradient exchange, max-over-ranks timing, weak and strong scaling.
 Short runs of a small batch -- what is checked is the plumbing and the line, not the number."""
@@ -10,6 +10,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +36,9 @@ COMMON = ["--steps", "10", "--warmup", "5", "--rays", "1024", "--teacher-pretrai
 
 
 def test_single_gpu_line_carries_the_contract():
-    d = _line([sys.executable, "bench.py", *COMMON, "--cpu-steps", "1", "--psnr-schedule", "300,40,80,200"])
+    # the live in-step stamps come from the forked recording, which the package makes by itself only under the hardware-queue
+    # setting it was validated with (pvd_hip.forked_graphs_ok): a caller's GPU_MAX_HW_QUEUES must not turn this check off
+    d = _line([sys.executable, "bench.py", "--full", *COMMON, "--cpu-steps", "1", "--psnr-schedule", "300,40,80,200"], env={"PVD_FORKED_GRAPHS": "1"})
     assert d["n_gpus"] == 1 and d["steps"] == 10 and d["warmup"] == 5 and d["higher_is_better"] is True and d["scaling"] == "weak"
     assert d["unit"] == "rays/s" and d["vs_baseline"] is None and d["data"].startswith("synthetic")
     assert abs(d["value"] - 10 * 1024 / (d["ms_per_step"] * 10 / 1e3)) <= 1e-6 * d["value"]
@@ -68,6 +71,21 @@ def test_single_gpu_line_carries_the_contract():
     assert q["hip_vs_oracle_same_rays_db"] > 80.0, q["hip_vs_oracle_detail"]  # render-level parity: same rays, HIP vs CPU oracle, fp32
 
 
+def test_plain_line_times_the_steps_and_dumps_what_the_last_one_returned(tmp_path):
+    """Without --full the line carries the headline alone (nothing is measured beyond the timed steps); --dump-outputs writes what
+    the last timed step returned -- loss, loss terms, student and teacher images -- as float32 arrays."""
+    d = _line([sys.executable, "bench.py", "--steps", "7", "--warmup", "3", "--rays", "1024", "--teacher-pretrain", "20",
+               "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["ms_per_step"] > 0 and d["config"]["capture_fallback"] is False
+    assert abs(d["value"] - 7 * 1024 / (d["ms_per_step"] * 7 / 1e3)) <= 1e-6 * d["value"]
+    assert all(d[k] is None for k in ("roofline", "sustained", "cpu_baseline", "gpu_reference", "psnr"))
+    arrays = {f[:-len(".npy")]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert {"loss", "loss_rgb", "pred_stu", "pred_tea"} <= set(arrays), sorted(arrays)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["pred_stu"].shape == arrays["pred_tea"].shape == (1, 1024, 3)
+    assert abs(arrays["loss"].item() - d["config"]["loss"]) <= 1e-6 * abs(d["config"]["loss"])
+
+
 def test_teacher_workload_line_has_a_cpu_baseline():
     d = _line([sys.executable, "bench.py", "--workload", "teacher", "--steps", "16", "--warmup", "32", "--rays", "1024", "--cpu-steps", "2"])
     assert d["metric"].startswith("train rays/s (hash teacher") and d["roofline"]["bytes_per_sample"] == 516
@@ -92,7 +110,7 @@ def test_teacher_workload_from_a_blender_scene_on_disk(tmp_path):
 @pytest.mark.parametrize("strong", [False, True])
 def test_two_ranks_as_the_driver_launches_them(strong):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", *COMMON] + (["--strong"] if strong else [])
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--full", *COMMON] + (["--strong"] if strong else [])
     d = _line(cmd, env={"PVD_DIST_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["steps"] == 10 and d["scaling"] == ("strong" if strong else "weak")
     per_gpu = 512 if strong else 1024
@@ -131,7 +149,7 @@ def test_the_eight_gpu_configurations_in_their_two_rank_form(name, extra):
     the hash table's gradient -- the latter arrives in half precision and is widened for the exchange --, loss sums, MAX over ranks,
     one line) on two ranks sharing the GPU over gloo, as the driver launches them."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", *COMMON, *extra]
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--full", *COMMON, *extra]
     d = _line(cmd, env={"PVD_DIST_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "ray-dp2" and d["scaling"] == "weak", name
     assert d["value"] > 0 and math.isfinite(d["config"]["loss"]) and d["config"]["capture_fallback"] is False, name

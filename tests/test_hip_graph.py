@@ -14,6 +14,14 @@ def _workload(seed=0):
     return DistillWorkload(hip_ops(), torch.device("cuda:0"), opt, teacher_pretrain_steps=30, seed=seed)
 
 
+@pytest.fixture
+def forked_recording(monkeypatch):
+    """The tests that check the forked recording (next step's prefix on a parallel chain) ask for it: the package records it by
+    itself only under the hardware-queue setting it was validated with (pvd_hip.forked_graphs_ok), and a caller's
+    GPU_MAX_HW_QUEUES takes precedence over that setting."""
+    monkeypatch.setenv("PVD_FORKED_GRAPHS", "1")
+
+
 def test_graph_replay_trains_and_advances_device_state():
     w = _workload()
     torch.cuda.manual_seed(7)
@@ -53,7 +61,7 @@ def test_graph_and_eager_agree_on_the_same_batches():
     assert np.allclose(la, lb[3:6], rtol=1e-3), (la, lb)
 
 
-def test_several_steps_per_graph_launch_train_like_single_step_replays():
+def test_several_steps_per_graph_launch_train_like_single_step_replays(forked_recording):
     """enable_graph(steps_per_graph=3): one graph launch = three consecutive optimisation steps (batch generation, schedule,
     loss-rate decay and loss scale all live on the device, so the second and third step of a replay see their own state).
     Same seeds -> the same loss trajectory as single-step replays."""
@@ -75,7 +83,7 @@ def test_several_steps_per_graph_launch_train_like_single_step_replays():
     assert float(wa.trainer.optimizer.param_groups[0]["lr"]) == pytest.approx(float(wb.trainer.optimizer.param_groups[0]["lr"]), rel=1e-6)
 
 
-def test_two_part_update_in_the_pipelined_graph_leaves_the_single_launch_bits():
+def test_two_part_update_in_the_pipelined_graph_leaves_the_single_launch_bits(forked_recording):
     """Multi-step graph, fork at the start of the step: AdamW runs in two parts -- behind the scatter only what the backward can
     have written; the L1-only / still-decaying rows (`_warm_A`) one step later on the forked branch, from the scalars the step
     recorded (FlatAdamW.two_part, pvd_adamw_extras.snapshot / replay).  Those rows see no atomics, so against the same run with
@@ -124,7 +132,7 @@ def test_two_part_update_in_the_pipelined_graph_leaves_the_single_launch_bits():
     assert np.allclose(la, lb, rtol=2e-3) and abs(l1a - l1b) <= 1e-4 * abs(l1b) and abs(lea - leb) <= 2e-3 * abs(leb), (la, lb, l1a, l1b, lea, leb)
 
 
-def test_a_forked_recording_that_fails_falls_back_to_back_to_back_steps_that_train(monkeypatch):
+def test_a_forked_recording_that_fails_falls_back_to_back_to_back_steps_that_train(monkeypatch, forked_recording):
     """with the update in two parts by default, a forked recording that raises half way left the L1 partial sums laid
     out for two parts; the back-to-back fall-back (one launch per step, recorded without warm-up) then tripped over
     `the form of the update must be settled before a capture begins`.  Force the failure: the fall-back must record, replay

@@ -19,6 +19,6 @@ for l in open(sys.argv[1]):
     if m and m.group(1) == kernel:
         print(json.dumps({"kernel": kernel, "launches": int(m.group(2)), "mean_us": float(m.group(3)), "median_us": float(m.group(4)),
                           "samples_per_launch": d["config"]["padded_rows_per_step"], "source_sha16": kernel_source_sha16(),
-                          "command": "rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline",
+                          "command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline",
                           "ms_per_step_of_that_run": d["ms_per_step"]}, indent=1))
         break
