@@ -439,29 +439,30 @@ __device__ __forceinline__ float sigmoid_h(float pre) {
 template <int KIND>
 __global__ void __launch_bounds__(kHeadBlock) k_head_fwd(HeadArgs a) {
     extern __shared__ __align__(16) half_t lds[];
-    if (a.rows_dev) a.M = min(a.M, (uint32_t)max(*a.rows_dev, 0));
-    if (blockIdx.x * (kHeadBlock / 64) * 16u >= a.M) return;  // nothing for this workgroup: skip the weight staging too
+    // rows to compute; a.M stays the row stride of the hash head's level-major [14][M][2] input
+    const uint32_t rows = a.rows_dev ? min(a.M, (uint32_t)max(*a.rows_dev, 0)) : a.M;
+    if (blockIdx.x * (kHeadBlock / 64) * 16u >= rows) return;  // nothing for this workgroup: skip the weight staging too
     HeadLds<KIND> W;
     W.carve(lds);
     const uint32_t lane = threadIdx.x & 63u, hi = lane >> 4;
     const uint32_t wave = (blockIdx.x * kHeadBlock + threadIdx.x) >> 6;
     const uint32_t nwaves = gridDim.x * (kHeadBlock / 64);
-    const uint32_t ntiles = div_up(a.M, 16u);
+    const uint32_t ntiles = div_up(rows, 16u);
     // A cold launch is a chain of memory round trips of 1.5-2 us each (kernel arguments -> weight image -> first tile's inputs -> ...):
     // the launch costs 10 us whatever M (tools/bench_head.py, M = 64).  The packed image goes by LDS-DMA, every piece in flight at
     // once, and the first tile's inputs are requested BEHIND it in the same round trip (one wait for both).
     if (a.image) copy_image_dma_static<HeadLds<KIND>::halfs>(lds, a.image, threadIdx.x);
-    TileIn<KIND> nxt = load_tile_in<KIND>(a, (size_t)wave * 16 + (lane & 15), (size_t)wave * 16 + (lane & 15) < a.M, lane);
+    TileIn<KIND> nxt = load_tile_in<KIND>(a, (size_t)wave * 16 + (lane & 15), (size_t)wave * 16 + (lane & 15) < rows, lane);
     if (a.image) __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the DMA has landed before the barrier releases the readers
     else W.load(a, threadIdx.x, kHeadBlock);
     __syncthreads();
     for (uint32_t tile = wave; tile < ntiles; tile += nwaves) {
         const size_t b = (size_t)tile * 16 + (lane & 15);
-        const bool valid = b < a.M;
+        const bool valid = b < rows;
         const TileIn<KIND> in = nxt;
         if (tile + nwaves < ntiles) {
             const size_t bn = (size_t)(tile + nwaves) * 16 + (lane & 15);
-            nxt = load_tile_in<KIND>(a, bn, bn < a.M, lane);
+            nxt = load_tile_in<KIND>(a, bn, bn < rows, lane);
         }
         TileFwd t;
         head_forward_tile<KIND>(a, W, in, lane, t);
