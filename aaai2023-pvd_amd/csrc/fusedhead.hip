@@ -30,6 +30,7 @@
 // launch and leave as one partial per wave, summed by a second tiny kernel straight into the gradients.
 #include "dda.h"
 #include "infer_persistent.h"
+#include "../../include/pvd_hip_mlp.h"
 #include "grid_lookup.h"
 #include "head_dw_reduce.h"
 #include "head_pack.h"
@@ -1361,8 +1362,10 @@ __device__ __forceinline__ uint32_t mlp_dma_count(int halfs, uint32_t wave) {  /
     const int pieces = (halfs * 2 + 1023) / 1024, nw = (int)(kMlpBlock / 64);
     return pieces > (int)wave ? (uint32_t)(pieces - (int)wave + nw - 1) / (uint32_t)nw : 0u;
 }
+constexpr int kMlpBufHalfs = (kMlpMaxChunkHalfs + 7) & ~7;
 struct MlpStream {
-    half_t *buf[3];
+    half_t *base;        // three chunk buffers of kMlpBufHalfs (an address computed from q: a pointer array indexed by q % 3 lived in scratch)
+    __device__ __forceinline__ half_t *buf(uint32_t i) const { return base + i * (uint32_t)kMlpBufHalfs; }
     const half_t *next;  // source of the next chunk to FETCH
     uint32_t q;          // chunks computed so far
     uint32_t young;      // this wave's DMA instructions of the most recently requested chunk (q + 1)
@@ -1378,11 +1381,11 @@ struct MlpStream {
         // every wave is past its reads of buffer (q + 2) % 3 (chunk q - 1): refill it
         young = 0u;
         if (next2_halfs > 0) {
-            mlp_dma(buf[(q + 2u) % 3u], next, next2_halfs, tid);
+            mlp_dma(buf((q + 2u) % 3u), next, next2_halfs, tid);
             next += next2_halfs;
             young = mlp_dma_count(next2_halfs, tid >> 6);
         }
-        const half_t *cur = buf[q % 3u];
+        const half_t *cur = buf(q % 3u);
         q++;
         return cur;
     }
@@ -1407,40 +1410,33 @@ __device__ __forceinline__ void mlp_layer(MlpStream &st, const h4 (&pts)[kMlpTS]
     }
 }
 
-__global__ void __launch_bounds__(kMlpBlock, 1) k_mlp_fwd_fused(HeadArgs a, MlpArgs m) {
-    extern __shared__ __align__(16) half_t lds[];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, hi = lane >> 4, wave = tid >> 6;
-    constexpr int kBufHalfs = (kMlpMaxChunkHalfs + 7) & ~7;
-    MlpStream st;
-    st.buf[0] = lds; st.buf[1] = lds + kBufHalfs; st.buf[2] = lds + 2 * kBufHalfs; st.q = 0;
-    half_t *headw = lds + 3 * kBufHalfs;
-    HeadLds<KIND_HASH> W;
-    W.carve(headw);
-    // the first chunk of the first layer and the head's weights start moving now
-    constexpr int h_first = mlp_chunk_halfs(kMlpChunkRows, kMlpIn), h_hidden = mlp_chunk_halfs(kMlpChunkRows, kMlpW),
-                  h_skip = mlp_chunk_halfs(kMlpChunkRows, kMlpIn + kMlpW), h_last = mlp_chunk_halfs(32, kMlpW);
+// chunk sizes of the weight stream (halfs): first layer, hidden layer, skip layer, last layer (one chunk of 32 rows)
+constexpr int kMlpHFirst = mlp_chunk_halfs(kMlpChunkRows, kMlpIn), kMlpHHidden = mlp_chunk_halfs(kMlpChunkRows, kMlpW),
+              kMlpHSkip = mlp_chunk_halfs(kMlpChunkRows, kMlpIn + kMlpW), kMlpHLast = mlp_chunk_halfs(32, kMlpW);
+
+// a pass over the weight stream starts: the first two chunks of the first layer begin to move into buf[0] / buf[1] (buf[2] becomes
+// a DMA target at the first acquire).  Nothing of an earlier pass may still be read from or in flight into the two buffers.
+__device__ __forceinline__ void mlp_stream_begin(MlpStream &st, const MlpArgs &m, uint32_t tid) {
+    st.q = 0;
     st.next = m.wstream;
-    if (a.image) copy_image_dma<kMlpBlock>(headw, a.image, HeadLds<KIND_HASH>::halfs, tid);  // (older than every chunk: complete by the first acquire)
-    else W.load(a, tid, kMlpBlock);
-    mlp_dma(st.buf[0], st.next, h_first, tid);
-    st.next += h_first;
-    mlp_dma(st.buf[1], st.next, h_first, tid);
-    st.next += h_first;
-    st.young = mlp_dma_count(h_first, wave);
-    // ---- inputs of this wave's kMlpTS tiles
-    const size_t base = ((size_t)blockIdx.x * (kMlpBlock / 64) + wave) * (16 * kMlpTS);
-    h4 pts[kMlpTS][kMlpIn / 16];
-    float dir[kMlpTS][3];
+    mlp_dma(st.buf(0), st.next, kMlpHFirst, tid);
+    st.next += kMlpHFirst;
+    mlp_dma(st.buf(1), st.next, kMlpHFirst, tid);
+    st.next += kMlpHFirst;
+    st.young = mlp_dma_count(kMlpHFirst, tid >> 6);
+}
+
+// The trunk and the head on this wave's kMlpTS 16-row tiles -- the ONE source of the model's arithmetic (k_mlp_fwd_fused: rows of
+// a batch; k_infer_mlp_persistent: rows of a local round).  pts / dir: the tiles' inputs, zeros for rows that do not exist (the
+// caller's predicate); emit(ts, t): what the caller keeps of tile ts.  A sample's output is one column of Y^T = W X^T: it does not
+// depend on the tile, wave or launch the sample sits in.  Every thread of the workgroup runs all of it (acquire is a workgroup
+// barrier and every wave issues its share of each chunk's DMA); on return no DMA is outstanding (the last acquire waits for all).
+template <class Emit>
+__device__ __forceinline__ void mlp_forward_tiles(const HeadArgs &a, const MlpArgs &m, MlpStream &st, const HeadLds<KIND_HASH> &W,
+                                                  const h4 (&pts)[kMlpTS][kMlpIn / 16], const float (&dir)[kMlpTS][3], uint32_t tid,
+                                                  uint32_t lane, Emit emit) {
+    constexpr int h_hidden = kMlpHHidden, h_skip = kMlpHSkip, h_last = kMlpHLast;
     const h4 hz = {(half_t)0, (half_t)0, (half_t)0, (half_t)0};
-#pragma unroll
-    for (int ts = 0; ts < kMlpTS; ts++) {
-        const size_t b = base + 16 * ts + (lane & 15u);
-        const bool valid = b < a.M;
-#pragma unroll
-        for (int k = 0; k < kMlpIn / 16; k++) pts[ts][k] = valid ? *reinterpret_cast<const h4 *>(m.pts + b * kMlpIn + 16 * k + 4 * hi) : hz;
-#pragma unroll
-        for (int c = 0; c < 3; c++) dir[ts][c] = valid ? a.dirs[3 * b + c] : 0.f;
-    }
     h4 xa[kMlpTS][kMlpW / 16], xb[kMlpTS][kMlpW / 16];
 #pragma unroll
     for (int ts = 0; ts < kMlpTS; ts++)
@@ -1475,14 +1471,48 @@ __global__ void __launch_bounds__(kMlpBlock, 1) k_mlp_fwd_fused(HeadArgs a, MlpA
     // ---- sigma / colour head on each tile (weights: DMA'd at the start, visible since the first acquire's barrier)
 #pragma unroll
     for (int ts = 0; ts < kMlpTS; ts++) {
-        const size_t b = base + 16 * ts + (lane & 15u);
-        const bool valid = b < a.M;
         TileIn<KIND_HASH> in;
         in.x[0] = feat[ts][0]; in.x[1] = feat[ts][1];
         in.sraw = 0.f; in.dx = dir[ts][0]; in.dy = dir[ts][1]; in.dz = dir[ts][2];
         TileFwd t;
         head_forward_tile<KIND_HASH>(a, W, in, lane, t);
-        if (valid) {
+        emit(ts, t);
+    }
+}
+
+__global__ void __launch_bounds__(kMlpBlock, 1) k_mlp_fwd_fused(HeadArgs a, MlpArgs m) {
+    extern __shared__ __align__(16) half_t lds[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, hi = lane >> 4, wave = tid >> 6;
+    constexpr int kBufHalfs = kMlpBufHalfs;
+    MlpStream st;
+    st.base = lds;
+    half_t *headw = lds + 3 * kBufHalfs;
+    HeadLds<KIND_HASH> W;
+    W.carve(headw);
+    // rows_dev: the device-side row count of the inference rounds (a.M sizes the launch); a workgroup past it streams nothing
+    const uint32_t M = a.rows_dev ? min(a.M, (uint32_t)max(*a.rows_dev, 0)) : a.M;
+    if (a.rows_dev && (size_t)blockIdx.x * ((kMlpBlock / 64) * 16 * kMlpTS) >= M) return;
+    // the first chunks of the first layer and the head's weights start moving now
+    if (a.image) copy_image_dma<kMlpBlock>(headw, a.image, HeadLds<KIND_HASH>::halfs, tid);  // (older than every chunk: complete by the first acquire)
+    else W.load(a, tid, kMlpBlock);
+    mlp_stream_begin(st, m, tid);
+    // ---- inputs of this wave's kMlpTS tiles
+    const size_t base = ((size_t)blockIdx.x * (kMlpBlock / 64) + wave) * (16 * kMlpTS);
+    h4 pts[kMlpTS][kMlpIn / 16];
+    float dir[kMlpTS][3];
+    const h4 hz = {(half_t)0, (half_t)0, (half_t)0, (half_t)0};
+#pragma unroll
+    for (int ts = 0; ts < kMlpTS; ts++) {
+        const size_t b = base + 16 * ts + (lane & 15u);
+        const bool valid = b < M;
+#pragma unroll
+        for (int k = 0; k < kMlpIn / 16; k++) pts[ts][k] = valid ? *reinterpret_cast<const h4 *>(m.pts + b * kMlpIn + 16 * k + 4 * hi) : hz;
+#pragma unroll
+        for (int c = 0; c < 3; c++) dir[ts][c] = valid ? a.dirs[3 * b + c] : 0.f;
+    }
+    mlp_forward_tiles(a, m, st, W, pts, dir, tid, lane, [&](int ts, const TileFwd &t) {
+        const size_t b = base + 16 * ts + (lane & 15u);
+        if (b < M) {
             *reinterpret_cast<f4 *>(a.feat16 + b * 16 + 4 * hi) = t.F;
             if (hi == 0) {
                 a.sigma[b] = __expf(t.F.x);
@@ -1491,14 +1521,15 @@ __global__ void __launch_bounds__(kMlpBlock, 1) k_mlp_fwd_fused(HeadArgs a, MlpA
                 a.rgb[3 * b + 2] = sigmoid_h(t.out.z);
             }
         }
-    }
+    });
 }
+
+static constexpr size_t kMlpLdsBytes = (3 * (size_t)kMlpBufHalfs + (((size_t)HeadLds<KIND_HASH>::halfs + 7) & ~(size_t)7)) * sizeof(half_t);
 
 static int launch_mlp_fwd_fused(const HeadArgs &a, const MlpArgs &m, hipStream_t s) {
     const uint32_t per_wg = (kMlpBlock / 64) * 16 * kMlpTS;
     const uint32_t blocks = div_up(a.M, per_wg);
-    constexpr int kBufHalfs = (kMlpMaxChunkHalfs + 7) & ~7;
-    const size_t lds_bytes = (3 * (size_t)kBufHalfs + (((size_t)HeadLds<KIND_HASH>::halfs + 7) & ~(size_t)7)) * sizeof(half_t);
+    const size_t lds_bytes = kMlpLdsBytes;
     static bool attr_set = false;
     if (!attr_set) {  // > 64 KB of dynamic LDS needs the opt-in
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_mlp_fwd_fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
@@ -1506,6 +1537,99 @@ static int launch_mlp_fwd_fused(const HeadArgs &a, const MlpArgs &m, hipStream_t
         attr_set = true;
     }
     hipLaunchKernelGGL(k_mlp_fwd_fused, dim3(blocks), dim3(kMlpBlock), lds_bytes, s, a, m);
+    return check_launch();
+}
+
+// ---- the eval branch's round loop of a frozen `mlp` model as ONE persistent launch (pvd_infer_image_mlp).
+// The slot machinery is infer_persistent_loop's (kMlpInfRays ray slots, rounds of up to kMlpInfRows = 4 waves x kMlpTS tiles x 16
+// sample rows: what one pass over the weight stream shades).  shade(rows): the positional encoding of the round's rows with
+// k_freq_encode's expressions (freqencoder.hip) into an LDS tile that borrows buf[2] -- not a DMA target before the pass's first
+// acquire -- then mlp_forward_tiles, the plain launch's arithmetic; sigma / rgb stay in LDS for the blend.  Per row the values are
+// pvd_freq_encode's + pvd_mlp_head_forward_fused's and per ray the round loop's, bit for bit (tests/test_hip_infer_mlp.py).
+// Every round, full or not, streams the whole trunk from L2: rows per round is what the speed hangs on.  Ray slots per workgroup,
+// 800 x 800 view, ms per launch / rows per shading round (profiles/infer_mlp_render.txt): 32: 18.7 / 140, 48: 17.6 / 144, 64: 17.2 /
+// 148, 96: 16.6 / 151, 128: 21.1 / 112 (more than 96 live slots take one sample each: at most 128 rows), 192: 17.0 / 148.
+#ifndef PVD_INFER_MLP_RAYS
+#define PVD_INFER_MLP_RAYS 96
+#endif
+struct MlpFreqs { float f[10]; };
+constexpr uint32_t kMlpInfRays = PVD_INFER_MLP_RAYS, kMlpInfRows = (kMlpBlock / 64) * 16 * kMlpTS;
+constexpr int kMlpPeStride = kMlpIn + 4;  // halfs: 34 dwords per row, the 16 rows of an 8-byte fragment read start on 16 different bank pairs
+static_assert(kMlpInfRays <= kMlpInfRows && kMlpInfRays <= kMlpBlock, "a round of n_step = 1 must fit the tile: one row per live slot");
+static_assert(kMlpInfRows * kMlpPeStride <= (uint32_t)kMlpBufHalfs, "the encoding tile borrows one chunk buffer");
+static_assert(kMlpLdsBytes % 16 == 0, "the slot machinery's floats follow the head's weight image");
+constexpr size_t kMlpInfLdsBytes = kMlpLdsBytes + sizeof(float) * InferTile::floats<kMlpInfRows, kMlpBlock>();
+static_assert(kMlpInfLdsBytes <= 160 * 1024, "chunk buffers + head image + round tile: one workgroup per CU, 160 KiB of LDS");
+
+__global__ void __launch_bounds__(kMlpBlock, 1) k_infer_mlp_persistent(HeadArgs a, MlpArgs m, MlpFreqs fb, InferImageArgs q) {
+    extern __shared__ __align__(16) half_t lds[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, hi = lane >> 4, wave = tid >> 6;
+    MlpStream st;
+    st.base = lds;
+    st.q = 0; st.young = 0; st.next = m.wstream;
+    half_t *headw = lds + 3 * kMlpBufHalfs;
+    HeadLds<KIND_HASH> W;
+    W.carve(headw);
+    InferTile T;
+    T.carve<kMlpInfRows, kMlpBlock>(reinterpret_cast<float *>(reinterpret_cast<char *>(lds) + kMlpLdsBytes));
+    if (a.image) { copy_image_dma<kMlpBlock>(headw, a.image, HeadLds<KIND_HASH>::halfs, tid); __builtin_amdgcn_s_waitcnt(0x0f70); }
+    else W.load(a, tid, kMlpBlock);
+    __syncthreads();  // the head's weights
+    half_t *pe = st.buf(2);  // [kMlpInfRows][kMlpPeStride] while a pass begins
+    infer_persistent_loop<kMlpInfRays, kMlpInfRows, kMlpBlock>(q, T, [&](uint32_t rows) {
+        // (the barriers around shade() separate this pass's DMA and tile from the last pass's reads and from the blend)
+        mlp_stream_begin(st, m, tid);
+        // ---- positional encoding, one thread per (row, frequency, dimension) as in k_freq_encode: unfused f32 product, sinf / cosf, f16
+        for (uint32_t i = tid; i < rows * 31u; i += kMlpBlock) {
+            const uint32_t row = i / 31u, j = i - row * 31u;
+            half_t *o = pe + row * kMlpPeStride;
+            if (j < 30u) {
+                const uint32_t k = j / 3u, d = j - k * 3u;
+                const float av = T.pos[3 * row + d] * fb.f[k];
+                o[3u + 6u * k + d] = (half_t)sinf(av);
+                o[3u + 6u * k + 3u + d] = (half_t)cosf(av);
+            } else {
+                for (uint32_t d = 0; d < 3; d++) o[d] = (half_t)T.pos[3 * row + d];
+                o[63] = (half_t)0.f;
+            }
+        }
+        __syncthreads();
+        // ---- this wave's tiles: rows 48 wave + 16 ts + (lane & 15); rows past the round's are fed zeros and written nowhere
+        h4 pts[kMlpTS][kMlpIn / 16];
+        float dir[kMlpTS][3];
+        const h4 hz = {(half_t)0, (half_t)0, (half_t)0, (half_t)0};
+#pragma unroll
+        for (int ts = 0; ts < kMlpTS; ts++) {
+            const uint32_t rw = wave * (16 * kMlpTS) + 16 * ts + (lane & 15u);
+            const bool valid = rw < rows;
+#pragma unroll
+            for (int k = 0; k < kMlpIn / 16; k++) pts[ts][k] = valid ? *reinterpret_cast<const h4 *>(pe + rw * kMlpPeStride + 16 * k + 4 * hi) : hz;
+            const uint32_t slot = valid ? T.row_slot[rw] : 0u;
+#pragma unroll
+            for (int c = 0; c < 3; c++) dir[ts][c] = valid ? T.sdir[3 * slot + c] : 0.f;
+        }
+        // (the first acquire's barrier comes behind every wave's reads of the tile: only then does chunk 2 start to land on it)
+        mlp_forward_tiles(a, m, st, W, pts, dir, tid, lane, [&](int ts, const TileFwd &t) {
+            const uint32_t rw = wave * (16 * kMlpTS) + 16 * ts + (lane & 15u);
+            if (rw < rows && hi == 0) {
+                T.sig[rw] = __expf(t.F.x);
+                T.rgb[3 * rw] = sigmoid_h(t.out.x); T.rgb[3 * rw + 1] = sigmoid_h(t.out.y); T.rgb[3 * rw + 2] = sigmoid_h(t.out.z);
+            }
+        });
+    });
+}
+
+static int launch_infer_mlp_persistent(const HeadArgs &a, const MlpArgs &m, const MlpFreqs &fb, const InferImageArgs &q, uint32_t N, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {  // > 64 KB of dynamic LDS needs the opt-in
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_infer_mlp_persistent), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kMlpInfLdsBytes) != hipSuccess)
+            return PVD_ERR_LAUNCH;
+        attr_set = true;
+    }
+    uint32_t blocks = div_up(N, kMlpInfRays);
+    if (blocks > 256u) blocks = 256u;  // persistent: the LDS allows one workgroup per CU
+    hipLaunchKernelGGL(k_infer_mlp_persistent, dim3(blocks), dim3(kMlpBlock), kMlpInfLdsBytes, s, a, m, fb, q);
     return check_launch();
 }
 
@@ -2145,9 +2269,10 @@ int pvd_infer_image_vm(const float *rays_o, const float *rays_d, const float *ne
     return check_launch();
 }
 
-int pvd_mlp_head_forward_fused(const void *pts_f16, uint32_t M, const void *wstream_f16, uint32_t n_before, uint32_t n_after, const float *dirs,
-                               const float *Wa1, const float *Wa2, const float *Wc1, const float *Wc2, const float *Wc3, const void *image,
-                               float clip_sigma_min, float clip_max, float *sigma, float *rgb, float *feat16, pvd_stream_t stream) {
+int pvd_mlp_head_forward_fused_rows(const void *pts_f16, uint32_t M, const void *wstream_f16, uint32_t n_before, uint32_t n_after, const float *dirs,
+                                    const float *Wa1, const float *Wa2, const float *Wc1, const float *Wc2, const float *Wc3, const void *image,
+                                    float clip_sigma_min, float clip_max, float *sigma, float *rgb, float *feat16, const int32_t *rows_dev,
+                                    pvd_stream_t stream) {
     if (M == 0) return PVD_OK;
     if (!pts_f16 || !wstream_f16 || !dirs || !Wa1 || !Wa2 || !Wc1 || !Wc2 || !Wc3 || !sigma || !rgb || !feat16) return PVD_ERR_INVALID;
     if (n_before > 16 || n_after > 16) return PVD_ERR_UNSUPPORTED;
@@ -2156,10 +2281,45 @@ int pvd_mlp_head_forward_fused(const void *pts_f16, uint32_t M, const void *wstr
     a.Wa1 = Wa1; a.Wa2 = Wa2; a.Wc1 = Wc1; a.Wc2 = Wc2; a.Wc3 = Wc3;
     a.clip_sigma_min = clip_sigma_min; a.clip_feat_min = clip_sigma_min; a.clip_max = clip_max;
     a.sigma = sigma; a.rgb = rgb; a.feat16 = feat16; a.image = (const half_t *)image;
-    a.rows_dev = nullptr;
+    a.rows_dev = rows_dev;
     MlpArgs m;
     m.pts = (const half_t *)pts_f16; m.wstream = (const half_t *)wstream_f16; m.n_before = n_before; m.n_after = n_after;
     return launch_mlp_fwd_fused(a, m, (hipStream_t)stream);
+}
+
+int pvd_mlp_head_forward_fused(const void *pts_f16, uint32_t M, const void *wstream_f16, uint32_t n_before, uint32_t n_after, const float *dirs,
+                               const float *Wa1, const float *Wa2, const float *Wc1, const float *Wc2, const float *Wc3, const void *image,
+                               float clip_sigma_min, float clip_max, float *sigma, float *rgb, float *feat16, pvd_stream_t stream) {
+    return pvd_mlp_head_forward_fused_rows(pts_f16, M, wstream_f16, n_before, n_after, dirs, Wa1, Wa2, Wc1, Wc2, Wc3, image, clip_sigma_min, clip_max,
+                                           sigma, rgb, feat16, nullptr, stream);
+}
+
+int pvd_infer_image_mlp(const float *rays_o, const float *rays_d, const float *nears, const float *fars, uint32_t N, const uint8_t *bitfield,
+                        float bound, float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H, float sigma_scale, const float *freq_bands_host,
+                        uint32_t n_freqs, const void *wstream_f16, uint32_t n_before, uint32_t n_after, const float *Wa1, const float *Wa2,
+                        const float *Wc1, const float *Wc2, const float *Wc3, const void *image, float clip_sigma_min, float clip_max,
+                        int32_t *workspace, float *weights_sum, float *depth, float *image_out, pvd_stream_t stream) {
+    if (N == 0) return PVD_OK;
+    if (!rays_o || !rays_d || !nears || !fars || !bitfield || !freq_bands_host || !wstream_f16 || !Wa1 || !Wa2 || !Wc1 || !Wc2 || !Wc3 || !workspace ||
+        !weights_sum || !depth || !image_out)
+        return PVD_ERR_INVALID;
+    if (max_steps == 0 || C == 0 || H == 0) return PVD_ERR_INVALID;
+    if (n_freqs != 10 || n_before > 16 || n_after > 16) return PVD_ERR_UNSUPPORTED;  // the structure fusedhead.mlp_supported() admits (PE = 10)
+    hipStream_t s = (hipStream_t)stream;
+    HeadArgs a;
+    a.x0 = nullptr; a.sigma_raw = nullptr; a.dirs = nullptr; a.M = 0;
+    a.Wa1 = Wa1; a.Wa2 = Wa2; a.Wc1 = Wc1; a.Wc2 = Wc2; a.Wc3 = Wc3;
+    a.clip_sigma_min = clip_sigma_min; a.clip_feat_min = clip_sigma_min; a.clip_max = clip_max;
+    a.sigma = nullptr; a.rgb = nullptr; a.feat16 = nullptr; a.image = (const half_t *)image; a.rows_dev = nullptr;
+    MlpArgs m;
+    m.pts = nullptr; m.wstream = (const half_t *)wstream_f16; m.n_before = n_before; m.n_after = n_after;
+    MlpFreqs fb;
+    for (uint32_t k = 0; k < 10; k++) fb.f[k] = freq_bands_host[k];
+    InferImageArgs q;
+    const int prc = infer_prepare(q, rays_o, rays_d, nears, fars, N, bitfield, bound, dt_gamma, max_steps, C, H, sigma_scale, workspace, weights_sum,
+                                  depth, image_out, s);
+    if (prc != PVD_OK) return prc;
+    return launch_infer_mlp_persistent(a, m, fb, q, N, s);
 }
 
 static uint32_t head_bwd_waves(int kind, uint32_t M) {

@@ -177,8 +177,10 @@ def mlp_weight_stream(model):
 
 
 @torch.no_grad()
-def mlp_head_infer(model, x, d):
-    """(sigma, rgb, feature_sigma_color) of a frozen `mlp` model: positional encoding (one launch) + trunk and head (one launch)."""
+def mlp_head_infer(model, x, d, rows_dev=None):
+    """(sigma, rgb, feature_sigma_color) of a frozen `mlp` model: positional encoding (one launch) + trunk and head (one launch).
+    rows_dev: optional DEVICE int32 row count (inference rounds): only the first min(M, rows_dev) rows of the trunk + head launch are
+    computed (the encoding runs over all M rows; those past the count are never read)."""
     enc = model.encoder_nerf_pe
     M = x.shape[0]
     pts = pvd_hip.freq_encode(x.reshape(-1, 3).float().contiguous(), enc.freq_bands, enc.include_input, torch.float16, 64)
@@ -189,8 +191,33 @@ def mlp_head_infer(model, x, d):
     n_before = model.skips
     n_after = len(model.nerf_mlp) - 3 - n_before
     pvd_hip.mlp_head_forward_fused(pts, mlp_weight_stream(model), n_before, n_after, d.float().contiguous(), M, *ws, a.sigma_clip_min,
-                                   a.sigma_clip_max, sigma, rgb, feat, image=_cached_image(model, KIND_HASH, ws, ps))
+                                   a.sigma_clip_max, sigma, rgb, feat, image=_cached_image(model, KIND_HASH, ws, ps), rows_dev=rows_dev)
     return sigma, rgb, feat
+
+
+@torch.no_grad()
+def mlp_infer_image(model, rays_o, rays_d, nears, fars, dt_gamma, max_steps):
+    """(weights_sum, depth, image) of the eval branch's round loop (renderer.py:450-543) for a frozen `mlp` model, as ONE persistent
+    launch (pvd_infer_image_mlp): rays [N,3], nears / fars [N]; the accumulators as the loop leaves them (before background compositing)."""
+    assert mlp_supported(model) and len(model.encoder_nerf_pe.freq_bands) == 10 and model.encoder_nerf_pe.include_input, \
+        "the persistent mlp render expects the 63-wide encoding and the 256-wide trunk"
+    dev = rays_o.device
+    N = rays_o.shape[0]
+    a = model.args
+    ws = [_w(model.sigma_net[0]), _w(model.sigma_net[1]), _w(model.color_net[0]), _w(model.color_net[1]), _w(model.color_net[2])]
+    ps = [model.sigma_net[0].weight, model.sigma_net[1].weight, model.color_net[0].weight, model.color_net[1].weight, model.color_net[2].weight]
+    image = _cached_image(model, KIND_HASH, ws, ps)
+    n_before = model.skips
+    n_after = len(model.nerf_mlp) - 3 - n_before
+    f32 = dict(dtype=torch.float32, device=dev)
+    weights_sum, depth, img = torch.zeros(N, **f32), torch.zeros(N, **f32), torch.zeros(N, 3, **f32)
+    workspace = torch.empty(2 * N + 12, dtype=torch.int32, device=dev)
+    model._last_infer_workspace = workspace  # (see hash_infer_image)
+    pvd_hip.infer_image_mlp(rays_o.float().contiguous(), rays_d.float().contiguous(), nears.float().contiguous(), fars.float().contiguous(),
+                            model.density_bitfield, float(model.bound), float(dt_gamma), int(max_steps), int(model.cascade), int(model.grid_size),
+                            float(model.density_scale), [float(f) for f in model.encoder_nerf_pe.freq_bands], mlp_weight_stream(model),
+                            n_before, n_after, *ws, a.sigma_clip_min, a.sigma_clip_max, workspace, weights_sum, depth, img, image=image)
+    return weights_sum, depth, img
 
 
 @torch.no_grad()

@@ -339,8 +339,7 @@ class NeRFNetwork(NeRFRenderer):
                 out = fh.hash_head_train(self, x, d)  # teacher training / hash student
             elif (self.model_type == "mlp" and not torch.is_grad_enabled() and hasattr(fh, "features_head_infer")
                   and self.in_dim == 28 and self.sigma_net[0].weight.shape == (64, 28) and getattr(self.ops, "freq_encode", None) is not None):
-                if hasattr(fh, "mlp_head_infer") and fh.mlp_supported(self) and len(self.encoder_nerf_pe.freq_bands) == 10 \
-                        and os.environ.get("PVD_MLP_FUSED", "1") != "0":
+                if self._mlp_fused_ok():
                     out = fh.mlp_head_infer(self, x, d)  # frozen NeRF-MLP teacher: positional encoding, then trunk + head in one launch
                 else:
                     out = fh.features_head_infer(self, self.forward_nerf_mlp(x), d)  # library GEMMs for the trunk, then the fused head
@@ -400,8 +399,20 @@ class NeRFNetwork(NeRFRenderer):
         self.color_l = color
         return sigma, color
 
+    def _mlp_fused_ok(self):
+        """The `mlp` structure the one-launch trunk + head implements (fusedhead.mlp_supported, PE = 10); PVD_MLP_FUSED=0: library GEMMs."""
+        fh = self.ops.fused_head
+        return (hasattr(fh, "mlp_head_infer") and fh.mlp_supported(self) and len(self.encoder_nerf_pe.freq_bands) == 10
+                and os.environ.get("PVD_MLP_FUSED", "1") != "0")
+
     def supports_device_rows(self):
-        """True if forward_rows() exists for this model here: hash and VM models on the HIP operator set under autocast."""
+        """True if forward_rows() exists for this model here: hash and VM models on the HIP operator set under autocast, and the
+        `mlp` model where forward() takes the one-launch trunk + head (the same condition)."""
+        if self.model_type == "mlp":
+            fh = getattr(self.ops, "fused_head", None)
+            return (fh is not None and self.bg_net is None and hasattr(fh, "features_head_infer") and self.in_dim == 28
+                    and self.sigma_net[0].weight.shape == (64, 28) and getattr(self.ops, "freq_encode", None) is not None
+                    and self._mlp_fused_ok())
         return (self.model_type in ("hash", "vm") and getattr(self.ops, "fused_head", None) is not None and self.bg_net is None
                 and (self.model_type != "vm" or getattr(self.ops, "vm_encode_infer", None) is not None)
                 and not (self.model_type == "hash" and not getattr(self.ops.fused_head, "FUSED_LOOKUP", False)))
@@ -413,6 +424,8 @@ class NeRFNetwork(NeRFRenderer):
         fh = self.ops.fused_head
         if self.model_type == "hash":
             sigma, rgb, _ = fh.hash_head_infer(self, x, d, rows_dev=rows_dev)
+        elif self.model_type == "mlp":
+            sigma, rgb, _ = fh.mlp_head_infer(self, x, d, rows_dev=rows_dev)
         else:
             sraw, prod = self.ops.vm_encode_infer(x, self._aabb(), *self.sigma_mat, *self.sigma_vec, *self.color_mat, *self.color_vec,
                                                   rows_dev=rows_dev)

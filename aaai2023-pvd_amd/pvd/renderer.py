@@ -259,13 +259,13 @@ class NeRFRenderer(nn.Module):
 
         # ---- inference: march / shade / composite in rounds with ray compaction (renderer.py:450-543)
         if self._persistent_render(rays_o, perturb):
-            # a frozen hash, VM or Plenoxel model: the whole loop as ONE persistent launch (pvd_infer_image_hash / _vm / _plenoxel;
-            # PVD_INFER_PERSISTENT=0: the rounds)
+            # a frozen hash, VM, Plenoxel or NeRF-MLP model: the whole loop as ONE persistent launch (pvd_infer_image_hash / _vm /
+            # _plenoxel / _mlp; PVD_INFER_PERSISTENT=0: the rounds)
             if self.model_type == "tensors":
                 run = self.ops.plenoxel.infer_image
             else:
                 fh = self.ops.fused_head
-                run = fh.hash_infer_image if self.model_type == "hash" else fh.vm_infer_image
+                run = {"hash": fh.hash_infer_image, "vm": fh.vm_infer_image}.get(self.model_type) or fh.mlp_infer_image
             weights_sum, depth, image = run(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps)
             image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
             depth = torch.clamp(depth - nears, min=0) / (fars - nears)
@@ -314,8 +314,10 @@ class NeRFRenderer(nn.Module):
             px = getattr(getattr(self, "ops", None), "plenoxel", None)
             return (rays_o.is_cuda and not perturb and hasattr(px, "infer_image") and getattr(self, "bg_net", None) is None
                     and not self.args.enable_edit_plenoxel)
+        # (mlp: supports_device_rows() holds only for the structure the fused trunk implements; any other keeps the host loop)
         return self._rounds_on_device(rays_o, perturb) and ((mt == "hash" and hasattr(fh, "hash_infer_image")) or
-                                                            (mt == "vm" and hasattr(fh, "vm_infer_image")))
+                                                            (mt == "vm" and hasattr(fh, "vm_infer_image")) or
+                                                            (mt == "mlp" and hasattr(fh, "mlp_infer_image")))
 
     # ------------------------------------------------------------------ inference rounds, state on the device
     def _rounds_on_device(self, rays_o, perturb):

@@ -88,7 +88,9 @@ ENTRY_POINTS = (
     "pvd_distill_sumsq", "pvd_distill_loss_final", "pvd_distill_sumsq_backward", "pvd_distill_loss_backward", "pvd_grid_set_variant", "pvd_grid_set_fwd_kernel",
     "pvd_adamw_step", "pvd_adamw_step_ex", "pvd_adamw_lazy_flush", "pvd_freq_encode", "pvd_mlp_head_forward_fused", "pvd_check_finite", "pvd_check_finite_f16", "pvd_check_finite_mixed", "pvd_l1_ranges", "pvd_segments_op", "pvd_segments_gather_zero_check",
 )
-for _name in ENTRY_POINTS:
+# ... and the entry points of include/pvd_hip_mlp.h (tests/test_abi_mlp.py)
+ENTRY_POINTS_MLP = ("pvd_mlp_head_forward_fused_rows", "pvd_infer_image_mlp")
+for _name in ENTRY_POINTS + ENTRY_POINTS_MLP:
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
@@ -840,20 +842,55 @@ def infer_image_vm(rays_o, rays_d, nears, fars, bitfield, bound, dt_gamma, max_s
           _p(image_out))
 
 
+def _mlp_stream_halfs(n_before, n_after):
+    return 4 * (64 * 72 + 64) + (n_before + n_after) * 4 * (64 * 264 + 64) + 4 * (64 * 328 + 64) + (32 * 264 + 32)  # rows x (K + 8) + biases
+
+
 def mlp_head_forward_fused(pts16, wstream, n_before, n_after, dirs, M, Wa1, Wa2, Wc1, Wc2, Wc3, clip_sigma_min, clip_max, sigma, rgb, feat16,
-                           image=None):
-    """pvd_mlp_head_forward_fused: the frozen NeRF-MLP model (trunk + head) in one launch; see include/pvd_hip.h."""
+                           image=None, rows_dev=None):
+    """pvd_mlp_head_forward_fused: the frozen NeRF-MLP model (trunk + head) in one launch; see include/pvd_hip.h.
+    rows_dev: optional DEVICE int32 row count (pvd_mlp_head_forward_fused_rows, include/pvd_hip_mlp.h): only the first
+    min(M, rows_dev) rows are computed and written."""
     dev = _dev(pts16, wstream, dirs, Wa1, Wa2, Wc1, Wc2, Wc3, sigma, rgb, feat16, image)
     _want(pts16, torch.float16, "pts16"), _want(wstream, torch.float16, "wstream")
     _f32_all(dirs=dirs, Wa1=Wa1, Wa2=Wa2, Wc1=Wc1, Wc2=Wc2, Wc3=Wc3, sigma=sigma, rgb=rgb, feat16=feat16)
     if pts16.shape != (M, 64) or not pts16.is_contiguous() or not wstream.is_contiguous():
         raise PvdHipError("pts16 must be a contiguous [M, 64] f16 tensor")
-    need = 4 * (64 * 72 + 64) + (n_before + n_after) * 4 * (64 * 264 + 64) + 4 * (64 * 328 + 64) + (32 * 264 + 32)  # rows x (K + 8) + biases
+    need = _mlp_stream_halfs(n_before, n_after)
     if wstream.numel() != need:
         raise PvdHipError("weight stream has %d halfs, the layer structure needs %d" % (wstream.numel(), need))
     _check_image(KIND_HASH_CONST, image)
+    if rows_dev is not None:
+        if dirs.shape[0] < M or sigma.numel() < M or rgb.numel() < 3 * M or feat16.numel() < 16 * M:
+            raise PvdHipError("buffers shorter than M rows")
+        _call("pvd_mlp_head_forward_fused_rows", dev, _p(pts16), _u32(M), _p(wstream), _u32(n_before), _u32(n_after), _p(dirs), _p(Wa1), _p(Wa2),
+              _p(Wc1), _p(Wc2), _p(Wc3), _p(image), _f32(clip_sigma_min), _f32(clip_max), _p(sigma), _p(rgb), _p(feat16), _rows_dev(rows_dev, dev))
+        return
     _call("pvd_mlp_head_forward_fused", dev, _p(pts16), _u32(M), _p(wstream), _u32(n_before), _u32(n_after), _p(dirs), _p(Wa1), _p(Wa2),
           _p(Wc1), _p(Wc2), _p(Wc3), _p(image), _f32(clip_sigma_min), _f32(clip_max), _p(sigma), _p(rgb), _p(feat16))
+
+
+def infer_image_mlp(rays_o, rays_d, nears, fars, bitfield, bound, dt_gamma, max_steps, C, H, sigma_scale, freq_bands, wstream, n_before, n_after,
+                    Wa1, Wa2, Wc1, Wc2, Wc3, clip_sigma_min, clip_max, workspace, weights_sum, depth, image_out, image=None):
+    """pvd_infer_image_mlp: the eval branch's round loop of a frozen `mlp` model as one persistent launch; see include/pvd_hip_mlp.h.
+    freq_bands: the positional encoding's frequencies (host floats)."""
+    dev = _dev(rays_o, rays_d, nears, fars, bitfield, wstream, Wa1, Wa2, Wc1, Wc2, Wc3, workspace, weights_sum, depth, image_out, image)
+    _want(wstream, torch.float16, "wstream"), _want(workspace, torch.int32, "workspace"), _want(bitfield, torch.uint8, "bitfield")
+    _f32_all(rays_o=rays_o, rays_d=rays_d, nears=nears, fars=fars, Wa1=Wa1, Wa2=Wa2, Wc1=Wc1, Wc2=Wc2, Wc3=Wc3, weights_sum=weights_sum,
+             depth=depth, image_out=image_out)
+    N = rays_o.shape[0]
+    if rays_d.shape[0] < N or nears.numel() < N or fars.numel() < N or weights_sum.numel() < N or depth.numel() < N or image_out.numel() < 3 * N \
+            or workspace.numel() < 2 * N + 12:
+        raise PvdHipError("buffers shorter than N rays")
+    need = _mlp_stream_halfs(n_before, n_after)
+    if wstream.numel() != need:
+        raise PvdHipError("weight stream has %d halfs, the layer structure needs %d" % (wstream.numel(), need))
+    _check_image(KIND_HASH_CONST, image)
+    bands = (ctypes.c_float * max(1, len(freq_bands)))(*[float(f) for f in freq_bands])
+    _call("pvd_infer_image_mlp", dev, _p(rays_o), _p(rays_d), _p(nears), _p(fars), _u32(N), _p(bitfield), _f32(bound), _f32(dt_gamma),
+          _u32(max_steps), _u32(C), _u32(H), _f32(sigma_scale), bands, _u32(len(freq_bands)), _p(wstream), _u32(n_before), _u32(n_after),
+          _p(Wa1), _p(Wa2), _p(Wc1), _p(Wc2), _p(Wc3), _p(image), _f32(clip_sigma_min), _f32(clip_max), _p(workspace), _p(weights_sum),
+          _p(depth), _p(image_out))
 
 
 KIND_HASH_CONST = 0
