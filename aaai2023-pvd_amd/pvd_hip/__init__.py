@@ -90,7 +90,9 @@ ENTRY_POINTS = (
 )
 # ... and the entry points of include/pvd_hip_mlp.h (tests/test_abi_mlp.py)
 ENTRY_POINTS_MLP = ("pvd_mlp_head_forward_fused_rows", "pvd_infer_image_mlp")
-for _name in ENTRY_POINTS + ENTRY_POINTS_MLP:
+# ... and the image metrics of include/pvd_hip_metrics.h (tests/test_abi_metrics.py)
+ENTRY_POINTS_METRICS = ("pvd_image_metrics_workspace_floats", "pvd_image_metrics")
+for _name in ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS:
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
@@ -1350,6 +1352,43 @@ def l1_ranges(p, ranges, scratch, out=None):
     b, e = _u64_array([r[0] for r in ranges]), _u64_array([r[1] for r in ranges])
     c = (ctypes.c_float * len(ranges))(*[float(r[2]) for r in ranges])
     _call("pvd_l1_ranges", dev, _p(p), b, e, c, _u32(len(ranges)), _p(scratch), _p(out))
+
+
+# --------------------------------------------------------------------------- image metrics (include/pvd_hip_metrics.h)
+METRICS_TILE = 32        # PVD_METRICS_TILE: the edge of the output tile one workgroup of the SSIM kernel computes
+METRICS_MAX_FILTER = 15  # PVD_METRICS_MAX_FILTER
+
+
+def image_metrics_workspace_floats(B, H, W, C):
+    n = int(_lib.pvd_image_metrics_workspace_floats(_u32(B), _u32(H), _u32(W), _u32(C)))
+    _check(min(n, 0), "pvd_image_metrics_workspace_floats")
+    return n
+
+
+def image_metrics(img0, img1, taps, k1, k2, max_val, workspace, ssim, mse, ssim_map=None, status=False):
+    """pvd_image_metrics: SSIM and mean squared error of the B image pairs img0 / img1 [B,H,W,C] f32 in one fused pass.
+    taps: the window (host floats); max_val None or <= 0: max(img0.max(), img1.max()) taken on the device (no read-back);
+    workspace: image_metrics_workspace_floats(B, H, W, C) floats; ssim / mse [B]; ssim_map [B,H,W,C] or None.
+    status=True returns the pvd_status instead of raising (PVD_ERR_UNSUPPORTED = -2: even or > 15 taps, C > 4)."""
+    dev = _dev(img0, img1, workspace, ssim, mse, ssim_map)
+    _f32_all(img0=img0, img1=img1, workspace=workspace, ssim=ssim, mse=mse)
+    if img0.dim() != 4 or img0.shape != img1.shape:
+        raise PvdHipError("img0 / img1 must be [B,H,W,C] tensors of one shape")
+    B, H, W, C = (int(v) for v in img0.shape)
+    if ssim_map is not None:
+        _want(ssim_map, torch.float32, "ssim_map")
+        if ssim_map.numel() != img0.numel():
+            raise PvdHipError("ssim_map must hold B*H*W*C floats")
+    if ssim.numel() < B or mse.numel() < B:
+        raise PvdHipError("ssim / mse must hold B floats")
+    if B and H and W and 0 < C <= 4 and workspace.numel() < image_metrics_workspace_floats(B, H, W, C):
+        raise PvdHipError("workspace too small: image_metrics_workspace_floats(B, H, W, C) floats are needed")
+    taps = [float(v) for v in taps]
+    rc = _invoke("pvd_image_metrics", dev, _p(img0), _p(img1), _u32(B), _u32(H), _u32(W), _u32(C), (ctypes.c_float * max(len(taps), 1))(*taps),
+                 _u32(len(taps)), _f32(k1), _f32(k2), _f32(0.0 if max_val is None else max_val), _p(workspace), _p(ssim), _p(mse), _p(ssim_map))
+    if status:
+        return rc
+    _check(rc, "pvd_image_metrics")
 
 
 raymarching_backend = types.SimpleNamespace(
