@@ -5,6 +5,7 @@
 // 64-wide wavefronts, 256-thread workgroups, ballot/scan compaction instead of
 // per-ray global atomics, and a deterministic prefix-sum slot allocator.
 #include "dda.h"
+#include "rays.h"
 
 #include <float.h>
 
@@ -14,35 +15,6 @@ constexpr uint32_t kBlock = 256;
 constexpr float kRPi = 0.3183098861837907f;
 
 // ------------------------------------------------------------------ utils
-
-// reference: kernel_near_far_from_aabb, raymarching.cu:93-147
-__device__ __forceinline__ void near_far_of(const float o[3], const float d[3], const float *__restrict__ aabb, float min_near, float &near,
-                                            float &far) {
-    float tn = 0.f, tf = 0.f;
-    bool miss = false;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float rd = 1.0f / d[a];
-        float lo = (aabb[a] - o[a]) * rd;
-        float hi = (aabb[a + 3] - o[a]) * rd;
-        if (lo > hi) { const float s = lo; lo = hi; hi = s; }
-        if (a == 0) {
-            tn = lo; tf = hi;
-        } else if (!miss) {
-            if (tn > hi || lo > tf) miss = true;
-            else {
-                if (lo > tn) tn = lo;
-                if (hi < tf) tf = hi;
-            }
-        }
-    }
-    if (miss) {
-        near = FLT_MAX; far = FLT_MAX;
-    } else {
-        near = tn < min_near ? min_near : tn;
-        far = tf;
-    }
-}
 
 __global__ void __launch_bounds__(kBlock) k_near_far(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                      const float *__restrict__ aabb, uint32_t N, float min_near,
@@ -70,22 +42,6 @@ __global__ void __launch_bounds__(kBlock) k_polar(const float *__restrict__ rays
     const float phi = atan2f(z, x);
     coords[2 * (size_t)n] = 2 * theta * kRPi - 1;
     coords[2 * (size_t)n + 1] = phi * kRPi;
-}
-
-
-// reference: get_rays, distill_mutual/utils.py:324-404 (pixel-centre directions through K^-1, normalise,
-// rotate by the camera-to-world pose).  One thread per ray instead of ~20 elementwise launches.
-__device__ __forceinline__ void ray_of_pixel(const float *__restrict__ pose, float fx, float fy, float cx, float cy, int64_t k, uint32_t W,
-                                             float o[3], float d[3]) {
-    const float i = (float)(k % W) + 0.5f, j = (float)(k / W) + 0.5f;
-    const float x = (i - cx) / fx, y = (j - cy) / fy, z = 1.0f;
-    const float inv = 1.0f / sqrtf(x * x + y * y + z * z);
-    const float dx = x * inv, dy = y * inv, dz = z * inv;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        d[r] = dx * pose[4 * r] + dy * pose[4 * r + 1] + dz * pose[4 * r + 2];
-        o[r] = pose[4 * r + 3];
-    }
 }
 
 __global__ void __launch_bounds__(kBlock) k_get_rays(const float *__restrict__ pose, float fx, float fy, float cx, float cy,

@@ -901,13 +901,16 @@ class TeacherTrainer(_TrainerBase):
         return torch.nn.functional.mse_loss(pred.float(), gt.float())
 
     # ---- a whole block of steps between two occupancy-grid updates as ONE captured graph
-    def _block_body(self, batches):
+    def _block_body(self, batches, source=None):
         o, m = self.opt, self.model
         it = {"k": 0}
 
         def body():
-            rays_o, rays_d, gt_rgb, bg_color = batches[it["k"] % len(batches)]
+            b = batches[it["k"] % len(batches)]
+            rays_o, rays_d, gt_rgb, bg_color = b
             it["k"] += 1
+            if source is not None:
+                source.fill(b)
             with torch.autocast(self.device_type, dtype=torch.float16, enabled=self.fp16 and self.device_type == "cuda"):
                 out = m.render(rays_o, rays_d, staged=False, bg_color=bg_color, perturb=True, force_all_rays=False,
                                dt_gamma=o.dt_gamma, max_steps=o.max_steps, num_steps=o.num_steps, upsample_steps=o.upsample_steps)
@@ -915,17 +918,23 @@ class TeacherTrainer(_TrainerBase):
                 loss = self._mse(pred, gt_rgb)
                 if o.l1_reg_weight > 0.0 and o.model_type == "vm":
                     loss = loss + self._l1_term()
+            if source is not None:
+                source.feedback(b, pred)
             return loss, pred
         return body
 
-    def _capture_block_pipelined(self, batches):
+    def _capture_block_pipelined(self, batches, source=None):
         """The block with step k + 1's march (near/far, count and write passes: ~50 us, instruction-bound, depends only on the
         occupancy grid, which is fixed inside a block) recorded on a forked stream next to step k's backward (the hash-grid
-        scatter sits at the memory-side atomic rate) and update -- the same schedule as DistillTrainer's multi-step graph."""
+        scatter sits at the memory-side atomic rate) and update -- the same schedule as DistillTrainer's multi-step graph.
+        With a `source`, step k + 1's batch is drawn on the forked stream directly before its march: the fork waits on the main
+        stream after step k's forward and feedback, so the draw sees the error map step k left."""
         o, m = self.opt, self.model
         kw = dict(dt_gamma=o.dt_gamma, max_steps=o.max_steps)
 
         def march(b):
+            if source is not None:
+                source.fill(b)
             with torch.autocast(self.device_type, dtype=torch.float16, enabled=self.fp16):
                 return m.march(b[0], b[1], perturb=True, force_all_rays=False, **kw)
 
@@ -952,6 +961,8 @@ class TeacherTrainer(_TrainerBase):
                     for k in range(K):
                         self._zero_grads(first_in_recording=k == 0)
                         self._static_out = loss_of(batches[k], marched)
+                        if source is not None:
+                            source.feedback(batches[k], self._static_out[1])
                         nxt = None
                         if k + 1 < K:
                             # (where this fork sits does not matter to the step: at its start, here, or between the head's backward
@@ -977,9 +988,11 @@ class TeacherTrainer(_TrainerBase):
         self._captured_occ_epoch = None
         self.pipelined_block = True
 
-    def capture_block(self, batches):
+    def capture_block(self, batches, source=None):
         """Capture `update_extra_interval` consecutive training steps (one per entry of `batches`: STATIC device tensors
-        (rays_o, rays_d, gt_rgb, bg) that the caller refills in place) as one HIP graph.  The teacher's sample budget moves
+        (rays_o, rays_d, gt_rgb, bg) that the caller refills in place) as one HIP graph.  With a `source` (pvd.batcher.DeviceBatcher;
+        `batches` its new_batch() slots) the refill is part of the graph: recorded step k is source.fill(batches[k]), render, loss,
+        source.feedback(batches[k], pred), backward, update -- every replay trains on 16 fresh batches.  The teacher's sample budget moves
         with every occupancy-grid update (mean_count, renderer.py:773-775); the captured steps therefore allocate a fixed
         number of sample rows (`fix_sample_alloc`) and read the budget rays are dropped against from device memory, so the
         graph survives the updates.  Call after at least one eager block (lazy initialisations, a measured mean_count)."""
@@ -987,12 +1000,12 @@ class TeacherTrainer(_TrainerBase):
         assert len(batches) == o.update_extra_interval == 16, "one batch per step of a block (the step counter has 16 slots)"
         assert m.cuda_ray and m.mean_count > 0 and self.global_step % o.update_extra_interval == 0
         m.fix_sample_alloc()
-        self._block_batches = batches
+        self._block_batches, self._block_source = batches, source
         self.pipelined_block = False
         if not self.dp.enabled and pvd_forked_graphs_ok():
             step0, local0 = self.global_step, m.local_step
             try:
-                self._capture_block_pipelined(batches)
+                self._capture_block_pipelined(batches, source)
             except Exception:
                 # the same join-and-fall-back DistillTrainer.capture_step has: the 16 steps recorded back to back (nothing ran
                 # during the failed recording, so the step counters are put back and no training step is lost or repeated)
@@ -1000,7 +1013,7 @@ class TeacherTrainer(_TrainerBase):
                 self.global_step, m.local_step = step0, local0
                 self.pipelined_block = False
         if not self.pipelined_block:
-            self.capture(self._block_body(batches), warmup=0, steps_per_graph=len(batches))
+            self.capture(self._block_body(batches, source), warmup=0, steps_per_graph=len(batches))
         self._block_alloc = m.sample_alloc
 
     def train_block(self):
@@ -1011,7 +1024,7 @@ class TeacherTrainer(_TrainerBase):
         aligned = m.mean_count + (128 - m.mean_count % 128)
         if getattr(m, "budget_exceeded", False) or aligned < 0.6 * m.sample_alloc:
             # the scene needs more rows than were captured (or far fewer: the padding rows cost time): capture again
-            self.capture_block(self._block_batches)
+            self.capture_block(self._block_batches, self._block_source)
         out = self.replay()
         m.local_step += self.steps_per_replay  # the replayed marches filled that many slots of the step counter
         return out[0].detach(), out[1]

@@ -92,7 +92,9 @@ ENTRY_POINTS = (
 ENTRY_POINTS_MLP = ("pvd_mlp_head_forward_fused_rows", "pvd_infer_image_mlp")
 # ... and the image metrics of include/pvd_hip_metrics.h (tests/test_abi_metrics.py)
 ENTRY_POINTS_METRICS = ("pvd_image_metrics_workspace_floats", "pvd_image_metrics")
-for _name in ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS:
+# ... and the device-side dataset batches of include/pvd_hip_data.h (tests/test_abi_data.py)
+ENTRY_POINTS_DATA = ("pvd_image_batch", "pvd_error_map_update")
+for _name in ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA:
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
@@ -1389,6 +1391,77 @@ def image_metrics(img0, img1, taps, k1, k2, max_val, workspace, ssim, mse, ssim_
     if status:
         return rc
     _check(rc, "pvd_image_metrics")
+
+
+# --------------------------------------------------------------------------- dataset batches (include/pvd_hip_data.h)
+DATA_MAX_GRID = 128  # PVD_DATA_MAX_GRID: the largest side of the coarse error-map grid
+
+
+def image_batch(images, poses, order, state, seed, fx, fy, cx, cy, N, aabb, min_near, error_map, view_out, inds, inds_coarse,
+                rays_o, rays_d, gt, bg, nears, fars, keys_out=None):
+    """pvd_image_batch: one training batch of N rays from one view of the uint8 stack images [V,H,W,3|4] (poses [V,4,4] f32).
+    order int32 [V] or None (identity); state int64 [3] device = {position in order, batch counter, 0}, advanced by the call;
+    error_map f32 [V, g*g] or None (uniform pixels); view_out int32 [1]; inds int64 [N]; inds_coarse int64 [N] (with the map);
+    rays_o, rays_d, gt [N,3]; bg [N,3] (None for RGB images: not touched); nears, fars [N]; keys_out f32 [g*g] or None."""
+    dev = _dev(images, poses, order, state, aabb, error_map, view_out, inds, inds_coarse, rays_o, rays_d, gt, bg, nears, fars, keys_out)
+    _want(images, torch.uint8, "images")
+    _f32_all(poses=poses, aabb=aabb, rays_o=rays_o, rays_d=rays_d, gt=gt, nears=nears, fars=fars)
+    _want(state, torch.int64, "state"), _want(view_out, torch.int32, "view_out"), _want(inds, torch.int64, "inds")
+    if images.dim() != 4 or images.shape[-1] not in (3, 4):
+        raise PvdHipError("images must be [V,H,W,3|4]")
+    V, H, W, C = (int(v) for v in images.shape)
+    N = int(N)
+    if poses.numel() != 16 * V or aabb.numel() < 6 or state.numel() < 3 or view_out.numel() < 1:
+        raise PvdHipError("poses must be [V,4,4], aabb [6], state int64 [3], view_out int32 [1]")
+    if order is not None:
+        _want(order, torch.int32, "order")
+        if order.numel() != V:
+            raise PvdHipError("order must hold V view ids")
+    if min(rays_o.numel(), rays_d.numel(), gt.numel()) < 3 * N or min(inds.numel(), nears.numel(), fars.numel()) < N:
+        raise PvdHipError("the outputs must hold N rays")
+    if C == 4:
+        if bg is None:
+            raise PvdHipError("RGBA images need bg [N,3]")
+    if bg is not None:
+        _want(bg, torch.float32, "bg")
+        if bg.numel() < 3 * N:
+            raise PvdHipError("bg must hold N colours")
+    g = 0
+    if error_map is not None:
+        _want(error_map, torch.float32, "error_map")
+        if error_map.dim() != 2 or error_map.shape[0] != V:
+            raise PvdHipError("error_map must be [V, g*g]")
+        g = int(round(error_map.shape[1] ** 0.5))
+        if g * g != error_map.shape[1]:
+            raise PvdHipError("error_map must be [V, g*g]")
+        if inds_coarse is None or inds_coarse.numel() < N:
+            raise PvdHipError("inds_coarse must hold N cells when an error map is given")
+        _want(inds_coarse, torch.int64, "inds_coarse")
+        if keys_out is not None:
+            _want(keys_out, torch.float32, "keys_out")
+            if keys_out.numel() < g * g:
+                raise PvdHipError("keys_out must hold g*g floats")
+    _call("pvd_image_batch", dev, _p(images), _p(poses), _p(order), _u32(V), _u32(H), _u32(W), _u32(C), _p(state),
+          ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _f32(fx), _f32(fy), _f32(cx), _f32(cy), _u32(N), _p(aabb), _f32(min_near),
+          _p(error_map), _u32(g), _p(view_out), _p(inds), _p(inds_coarse if error_map is not None else None), _p(rays_o), _p(rays_d),
+          _p(gt), _p(bg), _p(nears), _p(fars), _p(keys_out if error_map is not None else None))
+
+
+def error_map_update(error_map, view, inds_coarse, pred, gt, N):
+    """pvd_error_map_update: error_map[view[0]][inds_coarse[n]] = 0.1 old + 0.9 mean_c (pred - gt)^2 for the N rays of a batch
+    (error_map f32 [V, g*g]; view int32 [1] device; inds_coarse int64 [N], distinct; pred, gt f32 [N,3])."""
+    dev = _dev(error_map, view, inds_coarse, pred, gt)
+    _f32_all(error_map=error_map, pred=pred, gt=gt)
+    _want(view, torch.int32, "view"), _want(inds_coarse, torch.int64, "inds_coarse")
+    N = int(N)
+    if error_map.dim() != 2:
+        raise PvdHipError("error_map must be [V, g*g]")
+    g = int(round(error_map.shape[1] ** 0.5))
+    if g == 0 or g * g != error_map.shape[1]:
+        raise PvdHipError("error_map must be [V, g*g]")
+    if min(pred.numel(), gt.numel()) < 3 * N or inds_coarse.numel() < N or view.numel() < 1:
+        raise PvdHipError("view [1], inds_coarse [N], pred and gt [N,3] are needed")
+    _call("pvd_error_map_update", dev, _p(error_map), _u32(g), _p(view), _p(inds_coarse), _p(pred), _p(gt), _u32(N))
 
 
 raymarching_backend = types.SimpleNamespace(
