@@ -6,6 +6,7 @@
 // per-ray global atomics, and a deterministic prefix-sum slot allocator.
 #include "dda.h"
 #include "rays.h"
+#include "../../include/pvd_hip_march.h"
 
 #include <float.h>
 
@@ -380,12 +381,104 @@ __device__ __forceinline__ uint32_t march_ray_wave(const Dda &r, float t0, float
 
 constexpr uint32_t kRaysPerBlock = kBlock / kWave;
 
+// ------------------------------------------------------------------ coarse "may be occupied" mask
+// Most of a training batch's rays never meet an occupied cell, and a ray that does walks the whole empty stretch behind its
+// last sample: the count pass probes every lattice point of [t0, far) all the same.  Both cases are cut EXACTLY with a
+// coarse view of the bitfield: per cascade, one byte per block of 8^3 fine cells, set when the block or one of its 26
+// neighbours holds an occupied cell (pvd_occ_coarse_mask; plain linear order, (H/8)^3 bytes per cascade).
+constexpr uint32_t kCoarseShift = 3;
+static_assert((1u << kCoarseShift) == PVD_COARSE_BLOCK, "coarse block edge");
+
+// One thread per coarse block.  The 8^3 cells of a block are 512 consecutive Morton indices = 64 bytes of the bitfield.
+__global__ void __launch_bounds__(kBlock) k_occ_coarse_mask(const uint8_t *__restrict__ bitfield, uint32_t C, uint32_t H,
+                                                            uint8_t *__restrict__ mask) {
+    const uint32_t G = H >> kCoarseShift, G3 = G * G * G;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= C * G3) return;
+    const uint32_t c = i / G3, b = i - c * G3;
+    const uint32_t bx = b / (G * G), by = (b / G) % G, bz = b % G;
+    const uint8_t *cascade = bitfield + (size_t)c * ((size_t)H * H * H / 8);
+    uint32_t any = 0;
+    for (uint32_t x = max(bx, 1u) - 1u; x <= min(bx + 1u, G - 1u); x++)
+        for (uint32_t y = max(by, 1u) - 1u; y <= min(by + 1u, G - 1u); y++)
+            for (uint32_t z = max(bz, 1u) - 1u; z <= min(bz + 1u, G - 1u); z++) {
+                const uint4 *p = reinterpret_cast<const uint4 *>(cascade + (size_t)morton3(x, y, z) * 64u);
+#pragma unroll
+                for (int q = 0; q < 4; q++) { const uint4 v = p[q]; any |= v.x | v.y | v.z | v.w; }
+            }
+    mask[i] = any ? (uint8_t)1 : (uint8_t)0;
+}
+
+// The test in front of the walk (dt_gamma == 0 only; wave-uniform result).  Lane j takes s_j = t0 + j (far - t0) / 63 and
+// asks whether a lattice point NEAR s_j could be probed as occupied.  Returns false when the ray has to be walked unchanged
+// (no statement is made); otherwise `empty` says that no lattice point of the ray can be occupied, and, if not empty, `far`
+// is lowered to a value every possibly-occupied lattice point lies below.
+//
+// Why this misses nothing.  Every lattice point t the walk can probe has t0 <= t < far, hence a nearest s_j with
+// |t - s_j| <= step / 2, step = (far - t0) / 63.  The probe's position is clamp(o + t d) per axis (a single rounded fma, then a
+// clamp: monotone, error below 2^-23 bound), so the positions P of t and S of s_j differ per axis by at most
+// delta = max|d| step / 2, up to rounding: the s_j carry about 2^-22 far of error, which the guard span >= far / 1024 turns
+// into < 0.03 % of span against the 25 % by which delta is inflated below (0.2 % of span), and 2^-20 bound is added for the
+// positions' own rounding.  With that inflated delta:
+//   * the probe's level is max(level(max|P|), lvl_dt), level() monotone in its argument, and max|P| lies within delta of max|S|:
+//     the lane tries every level of [level(max|S| - delta), level(max|S| + delta)] (one, rarely two);
+//   * at one level the fine cell coordinate is a monotone, clamped function of the position with slope H / (2 mip_bound), so
+//     the cell coordinates of P and S differ by at most delta H / (2 mip_bound) <= 0.9 * 8 cells -- the per-ray condition checked
+//     first, at the smallest mip_bound; the 10 % left over dwarfs the cell arithmetic's rounding (H 2^-22 cells) -- and two
+//     coordinates less than 8 cells apart lie in the same or in adjacent blocks of 8: P's block is S's block or one of its 26
+//     neighbours, which the dilated mask covers.
+// So an occupied lattice point makes the lane of its nearest s_j hit.  No lane hits: nothing can be emitted.  Otherwise, with
+// j* the last hitting lane, every possibly-occupied t is at most s_j* + step / 2 (+ rounding) < s_j* + step: the walk may stop
+// there, because nothing leaves march_ray_wave's loop but the emitted samples and their records.
+__device__ __forceinline__ bool coarse_confine(const Dda &r, const uint8_t *__restrict__ mask, float t0, float &far, uint32_t lane,
+                                               bool &empty) {
+    empty = false;
+    if (!mask || r.dt_gamma != 0.0f) return false;
+    const float span = far - t0;
+    if (!(span >= far * (1.0f / 1024.0f)) || !(span > 1e-6f)) return false;
+    const float step = span * (1.0f / 63.0f);
+    const float dmax = fmaxf(fabsf(r.dx), fmaxf(fabsf(r.dy), fabsf(r.dz)));
+    const float delta = 1.25f * (0.5f * step * dmax) + r.bound * (1.0f / 1048576.0f);
+    const float edge0 = (float)(2u << kCoarseShift) * r.mip_bound0 * r.rH;  // world size of a coarse block at the finest level
+    if (!(delta <= 0.9f * edge0)) return false;  // (also NaN / Inf)
+
+    const float s = fmaf((float)lane, step, t0);
+    const float x = clampf(fmaf(s, r.dx, r.ox), -r.bound, r.bound);
+    const float y = clampf(fmaf(s, r.dy, r.oy), -r.bound, r.bound);
+    const float z = clampf(fmaf(s, r.dz, r.oz), -r.bound, r.bound);
+    int lo = 0, hi = 0;
+    if (!r.one_cascade) {
+        const float mx = fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z)));
+        int e_lo, e_hi, e_dt;
+        (void)frexpf(fmaxf(mx - delta, 0.0f), &e_lo);
+        (void)frexpf(mx + delta, &e_hi);
+        (void)frexpf((float)((double)(r.dt_const * r.Hf) * 0.5), &e_dt);  // as probe_impl, dt = dt_const
+        const int lvl_dt = (int)fminf(r.Cf - 1, fmaxf(0.0f, (float)e_dt));
+        lo = max((int)fminf(r.Cf - 1, fmaxf(0.0f, (float)e_lo)), lvl_dt);
+        hi = max((int)fminf(r.Cf - 1, fmaxf(0.0f, (float)e_hi)), lvl_dt);
+    }
+    const uint32_t G = r.H >> kCoarseShift;
+    bool hit = false;
+    for (int level = lo; level <= hi; level++) {
+        const float mip_rbound = 1.0f / fminf((float)(1 << level), r.bound);
+        const uint32_t bx = (uint32_t)(int)clampf(fmaf(x, mip_rbound, 1.0f) * r.half_h, 0.0f, r.cell_hi) >> kCoarseShift;
+        const uint32_t by = (uint32_t)(int)clampf(fmaf(y, mip_rbound, 1.0f) * r.half_h, 0.0f, r.cell_hi) >> kCoarseShift;
+        const uint32_t bz = (uint32_t)(int)clampf(fmaf(z, mip_rbound, 1.0f) * r.half_h, 0.0f, r.cell_hi) >> kCoarseShift;
+        hit = hit || mask[(size_t)level * G * G * G + (bx * G + by) * G + bz] != 0;
+    }
+    const uint64_t hits = __ballot(hit);
+    if (hits == 0) { empty = true; return true; }
+    const uint32_t last = 63u - (uint32_t)__clzll((long long)hits);
+    if (last < 63u) far = fminf(far, fmaf((float)(last + 1u), step, t0));
+    return true;
+}
+
 __global__ void __launch_bounds__(kBlock) k_march_count_wave(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                              const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps,
                                                              uint32_t N, uint32_t C, uint32_t H, const float *__restrict__ nears,
                                                              const float *__restrict__ fars, int32_t *__restrict__ rays, uint32_t perturb,
                                                              MarchRayRecords *__restrict__ records, const int32_t *__restrict__ counter,
-                                                             uint32_t fresh) {
+                                                             uint32_t fresh, const uint8_t *__restrict__ coarse_mask) {
     // the caller's running sample offset (fresh: the counter is scratch, the offset is zero)
     if (records && blockIdx.x == 0 && threadIdx.x == 0) records[N].n = fresh ? 0u : (uint32_t)counter[0];
     const uint32_t n = blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
@@ -398,9 +491,13 @@ __global__ void __launch_bounds__(kBlock) k_march_count_wave(const float *__rest
     Dda r;
     r.init(rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n, bound, dt_gamma, max_steps, C, H, grid);
     const float t0 = ray_t0(nears[n], r.dt_min, perturb, 42u, n);
-    const float far = fars[n];
+    float far = fars[n];
     uint32_t num;
-    if (t0 >= 0.0f && t0 < far) {
+    bool empty = false;
+    if (t0 >= 0.0f && t0 < far && coarse_confine(r, coarse_mask, t0, far, lane, empty) && empty) {
+        num = 0;  // no lattice point of the ray can lie in an occupied cell
+        if (records && lane == 0) { records[n].n = 0; records[n].overflow = 0u; }
+    } else if (t0 >= 0.0f && t0 < far) {  // (far: possibly lowered to just behind the last point that can)
         MarchRecord rec = {records ? records[n].chunk : nullptr, 0u, false};
 #ifdef PVD_MARCH_PROFILE
         num = march_ray_wave<false>(r, t0, far, max_steps, lane, nullptr, nullptr, nullptr, &prof_chunks, records ? &rec : nullptr);
@@ -1188,6 +1285,25 @@ int pvd_march_rays_train_ws(const float *rays_o, const float *rays_d, const uint
                             const float *fars, float *xyzs, float *dirs, float *deltas, int32_t *rays, int32_t *counter,
                             uint32_t perturb, void *workspace, size_t workspace_bytes, uint32_t flags, const int32_t *budget_dev,
                             pvd_stream_t stream) {
+    return pvd_march_rays_train_mask(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays,
+                                     counter, perturb, workspace, workspace_bytes, flags, budget_dev, nullptr, stream);
+}
+
+int pvd_occ_coarse_mask(const uint8_t *bitfield, uint32_t C, uint32_t H, uint8_t *mask, pvd_stream_t stream) {
+    PVD_REQUIRE(bitfield && mask && C >= 1 && C <= 16 && H >= 1 && H <= 1024);
+    // whole coarse blocks, and a block's 8^3 cells contiguous in a Morton order that stays inside the cascade: a power-of-two H
+    if ((H & (H - 1u)) || H < PVD_COARSE_BLOCK) return PVD_ERR_UNSUPPORTED;
+    PVD_REQUIRE((reinterpret_cast<uintptr_t>(bitfield) & 15u) == 0);
+    const uint32_t G = H >> kCoarseShift;
+    hipLaunchKernelGGL(k_occ_coarse_mask, dim3(div_up(C * G * G * G, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, bitfield, C, H, mask);
+    return check_launch();
+}
+
+int pvd_march_rays_train_mask(const float *rays_o, const float *rays_d, const uint8_t *grid, float bound, float dt_gamma,
+                              uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float *nears,
+                              const float *fars, float *xyzs, float *dirs, float *deltas, int32_t *rays, int32_t *counter,
+                              uint32_t perturb, void *workspace, size_t workspace_bytes, uint32_t flags,
+                              const int32_t *budget_dev, const uint8_t *coarse_mask, pvd_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const bool fresh = (flags & PVD_MARCH_FRESH) != 0;
     if (N == 0) {
@@ -1209,8 +1325,9 @@ int pvd_march_rays_train_ws(const float *rays_o, const float *rays_d, const uint
         (void)hipMemsetAsync(deltas, 0, 2 * (size_t)M * sizeof(float), s); (void)hipMemsetAsync(counter, 0, 2 * sizeof(int32_t), s);
     }
     const dim3 g(div_up(N, kRaysPerBlock)), b(kBlock);
+    if ((H & (H - 1u)) || H < PVD_COARSE_BLOCK) coarse_mask = nullptr;  // the mask exists for a power-of-two H >= 8 only
     hipLaunchKernelGGL(k_march_count_wave, g, b, 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, rays, perturb,
-                       records, counter, records && fresh ? 1u : 0u);
+                       records, counter, records && fresh ? 1u : 0u, coarse_mask);
     if (records) {  // two launches: the write pass rebuilds the samples from the chunk records and scans the counts itself
         hipLaunchKernelGGL(k_march_write_records, g, b, 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs,
                            dirs, deltas, rays, perturb, records, counter, fresh ? 1u : 0u, budget_dev);

@@ -78,6 +78,11 @@ class NeRFRenderer(nn.Module):
         if cuda_ray:
             self.register_buffer("density_grid", torch.zeros([self.cascade, grid_size ** 3]))
             self.register_buffer("density_bitfield", torch.zeros(self.cascade * grid_size ** 3 // 8, dtype=torch.uint8))
+            # the dilated coarse view of density_bitfield the training marcher skips empty rays and ray tails with (see
+            # coarse_mask): derived state at a fixed address (recorded graphs keep reading it), never saved
+            n_coarse = self.cascade * (grid_size // 8) ** 3 if grid_size >= 8 and grid_size & (grid_size - 1) == 0 else 0
+            self.register_buffer("density_coarse_mask", torch.zeros(n_coarse, dtype=torch.uint8), persistent=False)
+            self._coarse_mask_key = None
             self.mean_density = 0
             self.iter_density = 0
             self.register_buffer("step_counter", torch.zeros(16, 2, dtype=torch.int32))  # ring of 16 (renderer.py:108-113)
@@ -95,6 +100,25 @@ class NeRFRenderer(nn.Module):
 
     def note_occupancy_changed(self):
         self.occ_epoch += 1
+        if self.cuda_ray:
+            self._coarse_mask_key = None
+            self.coarse_mask()  # rebuilt where the bitfield is written, not in front of a march
+
+    def coarse_mask(self):
+        """density_coarse_mask, current, for march_rays_train(coarse_mask=) -- or None where there is none (an operator set
+        without the kernel, a grid size that is no power of two >= 8, buffers not on the GPU).  Every writer of density_bitfield
+        ends in note_occupancy_changed(), which rebuilds the mask in place with one launch on the current stream, right
+        behind the write.  The key (both addresses, the bitfield's autograd version) only catches a writer that did not:
+        a copy_ from outside, a module moved to another device.  It then costs a rebuild here instead of a wrong image."""
+        build = getattr(self.rm, "occ_coarse_mask", None)
+        mask, bits = self.density_coarse_mask, self.density_bitfield
+        if build is None or mask.numel() == 0 or not (bits.is_cuda and mask.is_cuda):
+            return None
+        key = (bits.data_ptr(), bits._version, mask.data_ptr())
+        if key != self._coarse_mask_key:
+            build(bits, self.cascade, self.grid_size, mask)
+            self._coarse_mask_key = key
+        return mask
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
@@ -218,14 +242,8 @@ class NeRFRenderer(nn.Module):
             budget = self._budget() if not force_all_rays else None  # (single-model training: the model composites its own march)
             own = i_march or bool(kwargs.get("own_march", False))  # the samples come from THIS model's march (budget applies)
             if i_march:
-                if budget is not None:
-                    xyzs, dirs, deltas, rays = rm.march_rays_train(rays_o, rays_d, self.bound, self.density_bitfield, self.cascade,
-                                                                   self.grid_size, nears, fars, counter, self.mean_count, perturb, 128,
-                                                                   force_all_rays, dt_gamma, max_steps, True, budget)
-                else:
-                    xyzs, dirs, deltas, rays = rm.march_rays_train(rays_o, rays_d, self.bound, self.density_bitfield, self.cascade,
-                                                                   self.grid_size, nears, fars, counter, self.mean_count, perturb, 128,
-                                                                   force_all_rays, dt_gamma, max_steps, True)
+                xyzs, dirs, deltas, rays = self._march_train(rays_o, rays_d, nears, fars, counter, perturb, force_all_rays, dt_gamma,
+                                                             max_steps, budget)
                 inherited_params = [xyzs, dirs, deltas, rays]
             else:
                 xyzs, dirs, deltas, rays = inherited_params
@@ -380,11 +398,17 @@ class NeRFRenderer(nn.Module):
         counter = self.step_counter[self.local_step % 16]  # "counter.zero_()" (renderer.py:374) = the scratch_counter flag below
         self.local_step += 1
         budget = self._budget() if not force_all_rays else None  # fixed allocation + device-side budget (fix_sample_alloc)
-        extra = (budget,) if budget is not None else ()
-        xyzs, dirs, deltas, rays = rm.march_rays_train(rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size,
-                                                       nears, fars, counter, self.mean_count, perturb, 128, force_all_rays, dt_gamma,
-                                                       max_steps, True, *extra)
+        xyzs, dirs, deltas, rays = self._march_train(rays_o, rays_d, nears, fars, counter, perturb, force_all_rays, dt_gamma, max_steps, budget)
         return [xyzs, dirs, deltas, rays], (nears, fars)
+
+    def _march_train(self, rays_o, rays_d, nears, fars, counter, perturb, force_all_rays, dt_gamma, max_steps, budget):
+        """march_rays_train on this model's occupancy grid, the way run_cuda calls it (align 128, the counter as scratch), with the
+        fixed allocation / device-side budget and the coarse mask where the model has them.  (An autograd Function takes positional
+        arguments only: the two optional ones are passed only where set, so an operator set without them is called as before.)"""
+        coarse = self.coarse_mask()
+        extra = () if budget is None and coarse is None else (budget,) if coarse is None else (budget, coarse)
+        return self.rm.march_rays_train(rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars,
+                                        counter, self.mean_count, perturb, 128, force_all_rays, dt_gamma, max_steps, True, *extra)
 
     def _cell_centres(self, coords, cas, jitter):
         """Grid coords [n,3] in [0,H) -> world positions of cascade `cas` (renderer.py:680-693)."""

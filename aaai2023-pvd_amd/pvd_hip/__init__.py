@@ -94,7 +94,9 @@ ENTRY_POINTS_MLP = ("pvd_mlp_head_forward_fused_rows", "pvd_infer_image_mlp")
 ENTRY_POINTS_METRICS = ("pvd_image_metrics_workspace_floats", "pvd_image_metrics")
 # ... and the device-side dataset batches of include/pvd_hip_data.h (tests/test_abi_data.py)
 ENTRY_POINTS_DATA = ("pvd_image_batch", "pvd_error_map_update")
-for _name in ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA:
+# ... and the coarse occupancy mask and the marcher that uses it, include/pvd_hip_march.h (tests/test_abi_march.py)
+ENTRY_POINTS_MARCH = ("pvd_occ_coarse_mask", "pvd_march_rays_train_mask")
+for _name in ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH:
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
@@ -270,17 +272,47 @@ def packbits(grid, N, density_thresh, bitfield):
     _call("pvd_packbits", dev, _p(grid), _u32(N), _f32(density_thresh), _p(bitfield))
 
 
+COARSE_BLOCK = 8  # PVD_COARSE_BLOCK (include/pvd_hip_march.h)
+
+
+def coarse_mask_bytes(C, H):
+    """Size of the coarse occupancy mask of a [C, H^3] bitfield, or 0 where it does not exist (H no power of two >= 8)."""
+    C, H = int(C), int(H)
+    return C * (H // COARSE_BLOCK) ** 3 if H >= COARSE_BLOCK and H & (H - 1) == 0 else 0
+
+
+def occ_coarse_mask(bitfield, C, H, mask):
+    """pvd_occ_coarse_mask: mask [C * (H/8)^3] u8 <- the dilated "may be occupied" blocks of bitfield [C * H^3 / 8] u8 (one launch)."""
+    dev = _dev(bitfield, mask)
+    _want(bitfield, torch.uint8, "bitfield"), _want(mask, torch.uint8, "mask")
+    C, H = int(C), int(H)
+    if coarse_mask_bytes(C, H) == 0 or mask.numel() != coarse_mask_bytes(C, H) or bitfield.numel() != C * H ** 3 // 8:
+        raise PvdHipError("mask must hold C * (H/8)^3 bytes and bitfield C * H^3 / 8 (H a power of two >= 8)")
+    _call("pvd_occ_coarse_mask", dev, _p(bitfield), _u32(C), _u32(H), _p(mask))
+
+
 def march_rays_train(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars,
-                     xyzs, dirs, deltas, rays, counter, perturb, use_workspace=True, fresh=False, budget_dev=None):
+                     xyzs, dirs, deltas, rays, counter, perturb, use_workspace=True, fresh=False, budget_dev=None, coarse_mask=None):
     """fresh: xyzs / dirs / deltas / counter are uninitialised scratch (PVD_MARCH_FRESH): the march itself writes zeros
     wherever no ray writes and overwrites the counter.  budget_dev: DEVICE int32 logical sample budget (rays are dropped
-    against min(M, budget); M rows are allocated), see include/pvd_hip.h."""
-    dev = _dev(rays_o, rays_d, grid, nears, fars, xyzs, dirs, deltas, rays, counter, budget_dev)
+    against min(M, budget); M rows are allocated), see include/pvd_hip.h.  coarse_mask: occ_coarse_mask of THIS grid (the
+    caller keeps it current): rays and ray tails that cannot meet an occupied cell are not walked; same results."""
+    dev = _dev(rays_o, rays_d, grid, nears, fars, xyzs, dirs, deltas, rays, counter, budget_dev, coarse_mask)
+    if coarse_mask is not None:
+        _want(coarse_mask, torch.uint8, "coarse_mask")
+        if coarse_mask.numel() != coarse_mask_bytes(C, H):
+            raise PvdHipError("coarse_mask must hold C * (H/8)^3 bytes")
     if budget_dev is not None:
         _want(budget_dev, torch.int32, "budget_dev")
     _f32_all(rays_o=rays_o, rays_d=rays_d, nears=nears, fars=fars, xyzs=xyzs, dirs=dirs, deltas=deltas)
     _want(grid, torch.uint8, "grid"), _want(rays, torch.int32, "rays"), _want(counter, torch.int32, "counter")
     ws = _march_workspace(dev, N) if use_workspace else None
+    if coarse_mask is not None:
+        _call("pvd_march_rays_train_mask", dev, _p(rays_o), _p(rays_d), _p(grid), _f32(bound), _f32(dt_gamma), _u32(max_steps),
+              _u32(N), _u32(C), _u32(H), _u32(M), _p(nears), _p(fars), _p(xyzs), _p(dirs), _p(deltas), _p(rays), _p(counter),
+              _u32(int(perturb)), _p(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0), _u32(1 if fresh else 0), _p(budget_dev),
+              _p(coarse_mask))
+        return
     _call("pvd_march_rays_train_ws", dev, _p(rays_o), _p(rays_d), _p(grid), _f32(bound), _f32(dt_gamma), _u32(max_steps),
           _u32(N), _u32(C), _u32(H), _u32(M), _p(nears), _p(fars), _p(xyzs), _p(dirs), _p(deltas), _p(rays), _p(counter),
           _u32(int(perturb)), _p(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0), _u32(1 if fresh else 0), _p(budget_dev))
@@ -1470,6 +1502,7 @@ raymarching_backend = types.SimpleNamespace(
     composite_objective_blocks=composite_objective_blocks,
     get_rays=get_rays, near_far_from_aabb=near_far_from_aabb, polar_from_ray=polar_from_ray, morton3D=morton3D,
     morton3D_invert=morton3D_invert, packbits=packbits, march_rays_train=march_rays_train,
+    occ_coarse_mask=occ_coarse_mask, coarse_mask_bytes=coarse_mask_bytes,
     composite_rays_train_forward=composite_rays_train_forward,
     composite_rays_train_backward=composite_rays_train_backward,
     march_rays=march_rays, composite_rays=composite_rays, compact_rays=compact_rays, MARCH_FRESH=MARCH_FRESH,

@@ -20,3 +20,6 @@ compact_rays = _ops.compact_rays
 # inference rounds whose state stays on the device (pvd_infer_*; the reference reads the alive count back every round)
 infer_round_begin, infer_compact, infer_march, infer_composite = _ops.infer_round_begin, _ops.infer_compact, _ops.infer_march, _ops.infer_composite
 INFER_STATE_INTS = _ops.INFER_STATE_INTS
+
+# coarse "may be occupied" mask of a density bitfield (pvd_occ_coarse_mask), for march_rays_train(..., coarse_mask=)
+occ_coarse_mask, coarse_mask_bytes = _ops.occ_coarse_mask, _ops.coarse_mask_bytes

@@ -96,7 +96,8 @@ def make_ops(backend, device_type="cuda"):
         @staticmethod
         @fwd32
         def forward(ctx, rays_o, rays_d, bound, density_bitfield, C, H, nears, fars, step_counter=None, mean_count=-1,
-                    perturb=False, align=-1, force_all_rays=False, dt_gamma=0, max_steps=1024, scratch_counter=False, budget=None):
+                    perturb=False, align=-1, force_all_rays=False, dt_gamma=0, max_steps=1024, scratch_counter=False, budget=None,
+                    coarse_mask=None):
             rays_o = _to_dev(rays_o).contiguous().view(-1, 3)
             rays_d = _to_dev(rays_d).contiguous().view(-1, 3)
             density_bitfield = _to_dev(density_bitfield).contiguous()
@@ -125,15 +126,19 @@ def make_ops(backend, device_type="cuda"):
                 step_counter = alloc(2, dtype=torch.int32, device=dev)  # point counter, ray counter
             elif scratch_counter and not fresh:
                 step_counter.zero_()
+            # coarse_mask: the dilated coarse view of density_bitfield its owner keeps (NeRFRenderer.coarse_mask); a caller
+            # without one passes None and every ray is walked in full.  Same samples either way.
+            # the extensions of the HIP backend, passed only where set (the reference's function set, and the oracle's, has none)
+            ext = {}
+            if fresh:
+                ext["fresh"] = True
             if budget_dev is not None:
-                backend.march_rays_train(rays_o, rays_d, density_bitfield, bound, dt_gamma, max_steps, N, C, H, M, nears, fars,
-                                         xyzs, dirs, deltas, rays, step_counter, perturb, fresh=fresh, budget_dev=budget_dev)
-            elif fresh:
-                backend.march_rays_train(rays_o, rays_d, density_bitfield, bound, dt_gamma, max_steps, N, C, H, M, nears, fars,
-                                         xyzs, dirs, deltas, rays, step_counter, perturb, fresh=True)
-            else:
-                backend.march_rays_train(rays_o, rays_d, density_bitfield, bound, dt_gamma, max_steps, N, C, H, M, nears, fars,
-                                         xyzs, dirs, deltas, rays, step_counter, perturb)
+                ext["budget_dev"] = budget_dev
+            if coarse_mask is not None:
+                assert hasattr(backend, "occ_coarse_mask"), "a coarse occupancy mask needs the HIP backend"
+                ext["coarse_mask"] = coarse_mask
+            backend.march_rays_train(rays_o, rays_d, density_bitfield, bound, dt_gamma, max_steps, N, C, H, M, nears, fars,
+                                     xyzs, dirs, deltas, rays, step_counter, perturb, **ext)
             # warm-up only: trim to the real count (D2H sync, :276-284)
             if force_all_rays or mean_count <= 0:
                 m = step_counter[0].item()
@@ -297,8 +302,10 @@ def make_ops(backend, device_type="cuda"):
             return tuple()
 
     extra = {}
+    if hasattr(backend, "occ_coarse_mask"):  # coarse "may be occupied" mask of a bitfield, for march_rays_train(coarse_mask=)
+        extra.update(occ_coarse_mask=backend.occ_coarse_mask, coarse_mask_bytes=backend.coarse_mask_bytes)
     if hasattr(backend, "infer_march"):  # inference rounds whose state stays on the device (pvd_infer_*; not in the reference)
-        extra = dict(infer_round_begin=backend.infer_round_begin, infer_compact=backend.infer_compact, infer_march=backend.infer_march,
+        extra.update(infer_round_begin=backend.infer_round_begin, infer_compact=backend.infer_compact, infer_march=backend.infer_march,
                      infer_composite=backend.infer_composite, INFER_STATE_INTS=backend.INFER_STATE_INTS)
     return types.SimpleNamespace(
         **extra,
