@@ -264,15 +264,17 @@ def test_grid_encode_backward_two_lane_kernel(hip, dev, coherent):
     g = (rng.randn(L, B, C) * 0.01).astype(np.float16)
     ge_ref, _ = oracle.grid_encode_backward(g, x, emb, offs, S, H)
     ref = ge_ref.astype(np.float32)
-    for knob in (0, 1 << 29):  # two lanes per sample (default) / thread per sample
-        hip.grid_set_fwd_kernel(2, 4096 | knob)
-        ge = torch.zeros(offs[-1], C, dtype=torch.float16, device=dev)
-        dummy = torch.zeros(1, dtype=torch.float16, device=dev)
-        hip.grid_encode_backward(t(g, dev), t(x, dev), t(emb, dev), t(offs, dev), ge, B, D, C, L, S, H, False, dummy, dummy, 0, False)
-        a = ge.float().cpu().numpy()
-        assert np.abs(a - ref).max() <= 2e-2 * np.abs(ref).max(), (knob, np.abs(a - ref).max(), np.abs(ref).max())
-        np.testing.assert_allclose(a.sum(), ref.sum(), rtol=5e-2, atol=1e-2)
-    hip.grid_set_fwd_kernel()
+    try:
+        for knob in (0, 1 << 29):  # two lanes per sample (default) / thread per sample
+            hip.grid_set_fwd_kernel(2, 4096 | knob)
+            ge = torch.zeros(offs[-1], C, dtype=torch.float16, device=dev)
+            dummy = torch.zeros(1, dtype=torch.float16, device=dev)
+            hip.grid_encode_backward(t(g, dev), t(x, dev), t(emb, dev), t(offs, dev), ge, B, D, C, L, S, H, False, dummy, dummy, 0, False)
+            a = ge.float().cpu().numpy()
+            assert np.abs(a - ref).max() <= 2e-2 * np.abs(ref).max(), (knob, np.abs(a - ref).max(), np.abs(ref).max())
+            np.testing.assert_allclose(a.sum(), ref.sum(), rtol=5e-2, atol=1e-2)
+    finally:  # the knob is process-wide: a failing assert must not leave it switched for the tests behind
+        hip.grid_set_fwd_kernel()
 
 
 @pytest.mark.parametrize("gridtype,align", [(0, False), (1, False), (0, True)])
@@ -290,12 +292,14 @@ def test_grid_encode_forward_paired_gathers_bit_exact(hip, dev, gridtype, align)
     x[5] = [1.5, 0.5, 0.5]  # out of range: zeros
     ref, _ = oracle.grid_encode_forward(x, emb, offs, S, H, gridtype=gridtype, align_corners=align)
     outs = []
-    for knob in (2, 0):
-        hip.grid_set_variant(knob)
-        out = torch.empty(L, B, C, dtype=torch.float16, device=dev)
-        hip.grid_encode_forward(t(x, dev), t(emb, dev), t(offs, dev), out, B, D, C, L, S, H, False, out, gridtype, align)
-        outs.append(out)
-    hip.grid_set_variant(0)
+    try:
+        for knob in (2, 0):
+            hip.grid_set_variant(knob)
+            out = torch.empty(L, B, C, dtype=torch.float16, device=dev)
+            hip.grid_encode_forward(t(x, dev), t(emb, dev), t(offs, dev), out, B, D, C, L, S, H, False, out, gridtype, align)
+            outs.append(out)
+    finally:
+        hip.grid_set_variant(0)
     assert torch.equal(outs[0], outs[1])
     assert np.array_equal(outs[0].cpu().numpy().view(np.uint16), np.ascontiguousarray(ref).view(np.uint16))
 
@@ -311,19 +315,21 @@ def test_grid_encode_forward_lanes_per_sample_kernels_bit_exact(hip, dev, gridty
     S = float(np.log2(pls))
     offs = _offsets(D, L, pls, H, 19, align)
     emb = _table(offs[-1], C, rng, np.float16)
-    for B in (30001, 77, 1):
-        x = rng.uniform(0, 1, (B, D)).astype(np.float32)
-        x[:1] = [[1.5, 0.5, 0.5]]  # out of range: zeros
-        if B > 10:
-            x[1:6] = [[0, 0, 0], [1, 1, 1], [0.5, 0.5, 0.5], [1, 0, 1], [0.999999, 0.25, 0.75]]
-        ref, _ = oracle.grid_encode_forward(x, emb, offs, S, H, gridtype=gridtype, align_corners=align)
-        ref_bits = np.ascontiguousarray(ref).view(np.uint16)
-        for lps, persist in ((2, 4096), (2, 0), (2, 96), (4, 0), (4, 1000), (2, 64 | (1 << 30)), (0, 0)):
-            hip.grid_set_fwd_kernel(lps, persist)
-            out = torch.full((L, B, C), 7.0, dtype=torch.float16, device=dev)
-            hip.grid_encode_forward(t(x, dev), t(emb, dev), t(offs, dev), out, B, D, C, L, S, H, False, out, gridtype, align)
-            assert np.array_equal(out.cpu().numpy().view(np.uint16), ref_bits), (B, lps, persist)
-    hip.grid_set_fwd_kernel()
+    try:
+        for B in (30001, 77, 1):
+            x = rng.uniform(0, 1, (B, D)).astype(np.float32)
+            x[:1] = [[1.5, 0.5, 0.5]]  # out of range: zeros
+            if B > 10:
+                x[1:6] = [[0, 0, 0], [1, 1, 1], [0.5, 0.5, 0.5], [1, 0, 1], [0.999999, 0.25, 0.75]]
+            ref, _ = oracle.grid_encode_forward(x, emb, offs, S, H, gridtype=gridtype, align_corners=align)
+            ref_bits = np.ascontiguousarray(ref).view(np.uint16)
+            for lps, persist in ((2, 4096), (2, 0), (2, 96), (4, 0), (4, 1000), (2, 64 | (1 << 30)), (0, 0)):
+                hip.grid_set_fwd_kernel(lps, persist)
+                out = torch.full((L, B, C), 7.0, dtype=torch.float16, device=dev)
+                hip.grid_encode_forward(t(x, dev), t(emb, dev), t(offs, dev), out, B, D, C, L, S, H, False, out, gridtype, align)
+                assert np.array_equal(out.cpu().numpy().view(np.uint16), ref_bits), (B, lps, persist)
+    finally:
+        hip.grid_set_fwd_kernel()
 
 
 @pytest.mark.parametrize("dtype,bound", [(np.float32, 1.0), (np.float16, 2.0), (np.float16, 1.0)])
