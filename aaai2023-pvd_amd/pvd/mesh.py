@@ -1,0 +1,99 @@
+"""A trained field as a triangle mesh, extracted on the device.
+
+reference: extract_fields / extract_geometry, distill_mutual/utils.py:442-488 -- a density volume of resolution^3 samples filled
+chunk by chunk through the host, mcubes.marching_cubes on the host, vertices mapped back into the box.  Here the volume is filled
+on the device and the surface is extracted by the kernels of csrc/mesh.hip (include/pvd_hip_mesh.h: marching tetrahedra on the
+Kuhn split; shared vertices, watertight, deterministic order); the two totals are the only values read back.
+"""
+import torch
+
+
+def _box(bmin, bmax, device):
+    lo = torch.as_tensor(bmin, dtype=torch.float32, device=device).reshape(3).contiguous()
+    hi = torch.as_tensor(bmax, dtype=torch.float32, device=device).reshape(3).contiguous()
+    return lo, hi
+
+
+@torch.no_grad()
+def density_field(query, R, bmin, bmax, chunk=1 << 21, device=None):
+    """u [R,R,R] f32 on the device, x-major as extract_fields fills it (utils.py:442-470): u[i,j,k] = query(point (i,j,k) of the
+    linspace^3 lattice of the box).  `query` maps [M,3] device points to M values, e.g. ``lambda x: model.density(x)["sigma"]``.
+    The points are made on the device, `chunk` at a time; nothing is copied to the host.  bmin / bmax: 3 floats or tensors."""
+    R = int(R)
+    if R < 2:
+        raise ValueError("R must be at least 2")
+    if device is None:
+        device = bmin.device if torch.is_tensor(bmin) else torch.device("cuda", torch.cuda.current_device())
+    lo, hi = _box(bmin, bmax, device)
+    # the lattice as the emit pass maps it back: lo + i / (R - 1) * (hi - lo)
+    axes = torch.arange(R, dtype=torch.float32, device=device)[:, None] / float(R - 1) * (hi - lo)[None, :] + lo[None, :]  # [R,3]
+    u = torch.empty(R, R, R, dtype=torch.float32, device=device)
+    flat = u.view(-1)
+    N = R ** 3
+    for s in range(0, N, int(chunk)):
+        n = torch.arange(s, min(s + int(chunk), N), dtype=torch.int64, device=device)
+        pts = torch.stack([axes[n // (R * R), 0], axes[(n // R) % R, 1], axes[n % R, 2]], dim=1)
+        flat[s:s + n.numel()] = query(pts).reshape(-1).to(torch.float32)
+    return u
+
+
+def extract_mesh(field, thresh, bmin, bmax):
+    """(vertices [V,3] f32, triangles [T,3] int32), device tensors, of the surface field = thresh (inside: field > thresh; normals
+    point outwards); field [R,R,R] f32 on the device, vertices in the box bmin .. bmax.  One read-back: the two totals."""
+    import pvd_hip
+    if field.dim() != 3 or field.shape[0] != field.shape[1] or field.shape[0] != field.shape[2]:
+        raise ValueError("field must be [R,R,R]")
+    field = field.contiguous()
+    R, dev = int(field.shape[0]), field.device
+    lo, hi = _box(bmin, bmax, dev)
+    ws = torch.empty(pvd_hip.mesh_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    totals = torch.zeros(2, dtype=torch.int32, device=dev)
+    pvd_hip.mesh_count(field, R, float(thresh), ws, totals)
+    V, T = (int(v) for v in totals.tolist())
+    vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
+    pvd_hip.mesh_emit(field, R, float(thresh), lo, hi, ws, vertices, triangles)
+    return vertices, triangles
+
+
+def default_threshold(model):
+    """min(density_thresh, mean_density) for a model with an occupancy grid -- the level its own marcher treats as empty
+    (renderer.py: update_extra_state) --, density_thresh otherwise.  A mean_density of 0 is what a model carries whose grid was
+    never updated (a student that marches on its teacher's grid): it says nothing, and density_thresh alone is used."""
+    thresh = float(model.density_thresh)
+    if getattr(model, "cuda_ray", False):
+        mean = float(model.mean_density)
+        if mean > 0.0:
+            thresh = min(thresh, mean)
+    return thresh
+
+
+def extract_geometry(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, return_field=False):
+    """reference: extract_geometry, utils.py:473-488, with the density of `model` as the query.  The box defaults to
+    model.aabb_infer, the threshold to default_threshold(model).  Returns (vertices, triangles) on the device (and the density
+    volume with return_field=True)."""
+    aabb = model.aabb_infer
+    lo = aabb[:3] if bmin is None else bmin
+    hi = aabb[3:] if bmax is None else bmax
+    if threshold is None:
+        threshold = default_threshold(model)
+    u = density_field(lambda x: model.density(x)["sigma"], resolution, lo, hi, chunk=chunk, device=aabb.device)
+    vertices, triangles = extract_mesh(u, threshold, lo, hi)
+    return (vertices, triangles, u) if return_field else (vertices, triangles)
+
+
+def write_ply(path, vertices, triangles):
+    """Binary little-endian PLY: float x y z per vertex, (uchar 3, int a b c) per face."""
+    import numpy as np
+    v = np.ascontiguousarray(vertices.detach().cpu().numpy() if torch.is_tensor(vertices) else vertices, dtype="<f4").reshape(-1, 3)
+    t = np.ascontiguousarray(triangles.detach().cpu().numpy() if torch.is_tensor(triangles) else triangles, dtype="<i4").reshape(-1, 3)
+    faces = np.empty(len(t), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    faces["n"] = 3
+    faces["v"] = t
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(t)))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(v.tobytes())
+        f.write(faces.tobytes())
+    return path

@@ -96,10 +96,13 @@ ENTRY_POINTS_METRICS = ("pvd_image_metrics_workspace_floats", "pvd_image_metrics
 ENTRY_POINTS_DATA = ("pvd_image_batch", "pvd_error_map_update")
 # ... and the coarse occupancy mask and the marcher that uses it, include/pvd_hip_march.h (tests/test_abi_march.py)
 ENTRY_POINTS_MARCH = ("pvd_occ_coarse_mask", "pvd_march_rays_train_mask")
-for _name in ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH:
+# ... and the triangle-mesh extraction of include/pvd_hip_mesh.h (tests/test_abi_mesh.py)
+ENTRY_POINTS_MESH = ("pvd_mesh_workspace_bytes", "pvd_mesh_count", "pvd_mesh_emit")
+for _name in ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH:
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -1494,6 +1497,55 @@ def error_map_update(error_map, view, inds_coarse, pred, gt, N):
     if min(pred.numel(), gt.numel()) < 3 * N or inds_coarse.numel() < N or view.numel() < 1:
         raise PvdHipError("view [1], inds_coarse [N], pred and gt [N,3] are needed")
     _call("pvd_error_map_update", dev, _p(error_map), _u32(g), _p(view), _p(inds_coarse), _p(pred), _p(gt), _u32(N))
+
+
+# --------------------------------------------------------------------------- triangle meshes (include/pvd_hip_mesh.h)
+MESH_MAX_R = 512  # PVD_MESH_MAX_R: lattice points per edge, 2 .. 512
+
+
+def mesh_workspace_bytes(R):
+    """pvd_mesh_workspace_bytes: bytes of workspace mesh_count / mesh_emit need for a field of R^3 samples."""
+    n = int(_lib.pvd_mesh_workspace_bytes(_u32(R))) if 0 <= int(R) < 2 ** 32 else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_workspace_bytes: R must be 2 .. %d, got %d" % (MESH_MAX_R, int(R)))
+    return n
+
+
+def _mesh_common(field, R, workspace):
+    _want(field, torch.float32, "field"), _want(workspace, torch.uint8, "workspace")
+    R = int(R)
+    if field.numel() != R ** 3:
+        raise PvdHipError("field must hold R^3 floats")
+    if workspace.numel() < mesh_workspace_bytes(R):
+        raise PvdHipError("workspace too small: mesh_workspace_bytes(R) bytes are needed")
+    return R
+
+
+def mesh_count(field, R, thresh, workspace, totals):
+    """pvd_mesh_count: the count pass and the two scans of the level set field > thresh (field [R,R,R] f32, x-major); leaves the
+    workspace (uint8, mesh_workspace_bytes(R)) as mesh_emit needs it; totals int32 [2] <- (vertices, triangles), on the device."""
+    dev = _dev(field, workspace, totals)
+    R = _mesh_common(field, R, workspace)
+    _want(totals, torch.int32, "totals")
+    if totals.numel() < 2:
+        raise PvdHipError("totals must hold 2 int32 values")
+    _call("pvd_mesh_count", dev, _p(field), _u32(R), _f32(thresh), _p(workspace), ctypes.c_size_t(workspace.numel()), _p(totals))
+
+
+def mesh_emit(field, R, thresh, bmin, bmax, workspace, vertices, triangles):
+    """pvd_mesh_emit: vertices [V,3] f32 (positions in the box bmin .. bmax, device f32 [3] each) and triangles [T,3] int32 of the
+    SAME field, R, thresh and the workspace mesh_count left; V and T are the totals it wrote (both 0: nothing is launched)."""
+    dev = _dev(field, workspace, bmin, bmax, vertices, triangles)
+    R = _mesh_common(field, R, workspace)
+    _f32_all(bmin=bmin, bmax=bmax, vertices=vertices)
+    _want(triangles, torch.int32, "triangles")
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    if vertices.numel() % 3 or triangles.numel() % 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    V, T = vertices.numel() // 3, triangles.numel() // 3
+    _call("pvd_mesh_emit", dev, _p(field), _u32(R), _f32(thresh), _p(bmin), _p(bmax), _p(workspace), ctypes.c_size_t(workspace.numel()),
+          _p(vertices), _u32(V), _p(triangles), _u32(T))
 
 
 raymarching_backend = types.SimpleNamespace(

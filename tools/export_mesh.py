@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""A checkpoint as a triangle mesh: the density of the model, sampled on a resolution^3 lattice of its inference box and meshed on
+the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
+
+  python tools/train_distill.py --save-student student.pth [--save-teacher teacher.pth]
+  python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
+
+The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
+The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean)."""
+import argparse
+import os
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
+
+from pvd.checkpoint import load_student_checkpoint  # noqa: E402
+from pvd.config import PVDConfig  # noqa: E402
+from pvd.mesh import default_threshold, extract_geometry, write_ply  # noqa: E402
+from pvd.ops import hip_ops  # noqa: E402
+from pvd.workload import make_model  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("checkpoint")
+    ap.add_argument("-o", "--out", default=None, help="PLY path (default: the checkpoint's name with .ply)")
+    ap.add_argument("--model-type", default="vm", choices=["hash", "mlp", "vm", "tensors"])
+    ap.add_argument("--resolution", type=int, default=256)
+    ap.add_argument("--threshold", type=float, default=None)
+    ap.add_argument("--resolution0", type=int, default=PVDConfig.resolution0, help="VM: initial resolution (the file's own is loaded)")
+    ap.add_argument("--plenoxel-res", default=PVDConfig.plenoxel_res)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    opt = PVDConfig(model_type=a.model_type, resolution0=a.resolution0, plenoxel_res=a.plenoxel_res)
+    model = make_model(hip_ops(), opt, a.model_type, False, dev)
+    missing, unexpected = load_student_checkpoint(model, None, a.checkpoint)
+    if missing or unexpected:
+        print("state-dict keys missing %s, unexpected %s" % (missing, unexpected), file=sys.stderr)
+    model.eval()
+    thresh = default_threshold(model) if a.threshold is None else a.threshold
+    vertices, triangles = extract_geometry(model, resolution=a.resolution, threshold=thresh)
+    out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
+    write_ply(out, vertices, triangles)
+    print("%s: %d vertices, %d triangles at density %.6g, resolution %d" % (out, vertices.shape[0], triangles.shape[0], thresh, a.resolution))
+
+
+if __name__ == "__main__":
+    main()

@@ -16,6 +16,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
 
+from pvd.checkpoint import save_checkpoint  # noqa: E402
 from pvd.config import PVDConfig  # noqa: E402
 from pvd.ops import hip_ops  # noqa: E402
 from pvd.scene import BLENDER_INTRINSICS, get_rays, synthetic_poses  # noqa: E402
@@ -53,6 +54,8 @@ def main():
     ap.add_argument("--stage1", type=int, default=500)
     ap.add_argument("--stage2", type=int, default=1500)
     ap.add_argument("--steps", type=int, default=6000)
+    ap.add_argument("--save-student", default=None, help="write the student's checkpoint here at the end (tools/export_mesh.py reads it)")
+    ap.add_argument("--save-teacher", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     opt = PVDConfig(model_type=a.student, iters=a.steps, stage_iters={"stage1": a.stage1, "stage2": a.stage2})
@@ -83,6 +86,11 @@ def main():
         st, sg, tg = evaluate(w, held_out)
         print("step %5d (stage %d)  train time %.2f s  PSNR / SSIM student vs teacher %.2f dB / %.4f, student vs GT %.2f dB / %.4f "
               "(teacher vs GT %.2f dB / %.4f)" % ((tr.global_step, tr._stage_of(max(tr.global_step - 1, 0)), t_train) + st + sg + tg), flush=True)
+    for path, model in ((a.save_student, w.stu), (a.save_teacher, w.tea)):
+        if path:
+            getattr(model, "_pvd_flush_params", lambda: None)()  # (a flat optimizer's deferred decays, before the tables are read)
+            save_checkpoint(path, model, global_step=tr.global_step)
+            print("wrote %s" % path, flush=True)
 
 
 if __name__ == "__main__":
