@@ -4,6 +4,10 @@ reference: extract_fields / extract_geometry, distill_mutual/utils.py:442-488 --
 chunk by chunk through the host, mcubes.marching_cubes on the host, vertices mapped back into the box.  Here the volume is filled
 on the device and the surface is extracted by the kernels of csrc/mesh.hip (include/pvd_hip_mesh.h: marching tetrahedra on the
 Kuhn split; shared vertices, watertight, deterministic order); the two totals are the only values read back.
+
+The reference's meshes carry the density "floaters" of the field as small closed shells (network.py:601: "lots of noisy outliers
+in hashnerf"); label_components / drop_components (csrc/components.hip, include/pvd_hip_components.h) take them out of the volume
+on the device before it is meshed.
 """
 import torch
 
@@ -56,6 +60,50 @@ def extract_mesh(field, thresh, bmin, bmax):
     return vertices, triangles
 
 
+def _cube(field):
+    if field.dim() != 3 or field.shape[0] != field.shape[1] or field.shape[0] != field.shape[2]:
+        raise ValueError("field must be [R,R,R]")
+    return field.contiguous(), int(field.shape[0])
+
+
+def label_components(field, thresh):
+    """(labels [R,R,R] int32, sizes [R,R,R] int32, stats) of the connected components of the set field > thresh, under the
+    connectivity of the mesher's Kuhn split (14 neighbours).  labels: the smallest linear index of the point's component, -1
+    outside; sizes: the component's number of points at its label, 0 elsewhere; both stay on the device.  stats, the one
+    read-back: (components, inside points, size of the largest component, its label) as Python ints."""
+    import pvd_hip
+    field, R = _cube(field)
+    labels = torch.empty(R, R, R, dtype=torch.int32, device=field.device)
+    sizes = torch.empty(R, R, R, dtype=torch.int32, device=field.device)
+    stats = torch.zeros(4, dtype=torch.int32, device=field.device)
+    pvd_hip.components_label(field, R, float(thresh), labels, sizes, stats)
+    return labels, sizes, tuple(int(v) for v in stats.tolist())
+
+
+def _drop(field, R, thresh, min_points, largest_only, out):
+    """-> (stats, kept) as device tensors; out <- the filtered field"""
+    import pvd_hip
+    dev = field.device
+    labels = torch.empty(R ** 3, dtype=torch.int32, device=dev)
+    sizes = torch.empty(R ** 3, dtype=torch.int32, device=dev)
+    stats = torch.zeros(4, dtype=torch.int32, device=dev)
+    kept = torch.zeros(2, dtype=torch.int32, device=dev)
+    pvd_hip.components_label(field, R, float(thresh), labels, sizes, stats)
+    pvd_hip.components_filter(field, labels, sizes, stats, R, float(thresh), int(min_points), bool(largest_only), out, kept)
+    return stats, kept
+
+
+def drop_components(field, thresh, min_points=0, largest_only=False):
+    """(field', kept): field with every point of a dropped component set to thresh, i.e. moved outside -- dropped are the components
+    of fewer than min_points points and, with largest_only, all but the largest one (ties: the one with the smaller label).  The
+    mesh of field' is the mesh of field without the shells of the dropped components, vertex bits included.  field is not changed.
+    kept, the one read-back: (components kept, points kept)."""
+    field, R = _cube(field)
+    out = torch.empty_like(field)
+    _, kept = _drop(field, R, thresh, min_points, largest_only, out)
+    return out, tuple(int(v) for v in kept.tolist())
+
+
 def default_threshold(model):
     """min(density_thresh, mean_density) for a model with an occupancy grid -- the level its own marcher treats as empty
     (renderer.py: update_extra_state) --, density_thresh otherwise.  A mean_density of 0 is what a model carries whose grid was
@@ -68,18 +116,27 @@ def default_threshold(model):
     return thresh
 
 
-def extract_geometry(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, return_field=False):
+def extract_geometry(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, return_field=False, min_points=0,
+                     largest_only=False, return_counts=False):
     """reference: extract_geometry, utils.py:473-488, with the density of `model` as the query.  The box defaults to
     model.aabb_infer, the threshold to default_threshold(model).  Returns (vertices, triangles) on the device (and the density
-    volume with return_field=True)."""
+    volume with return_field=True).  min_points > 0 or largest_only: the volume is filtered in place by drop_components' rule
+    between the two steps (the returned volume is the filtered one); return_counts=True then appends (components found,
+    components kept, points kept), None where nothing was filtered."""
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
     if threshold is None:
         threshold = default_threshold(model)
     u = density_field(lambda x: model.density(x)["sigma"], resolution, lo, hi, chunk=chunk, device=aabb.device)
+    counts = None
+    if int(min_points) > 0 or largest_only:
+        stats, kept = _drop(u, int(resolution), threshold, min_points, largest_only, u)
+        if return_counts:
+            counts = (int(stats[0]),) + tuple(int(v) for v in kept.tolist())
     vertices, triangles = extract_mesh(u, threshold, lo, hi)
-    return (vertices, triangles, u) if return_field else (vertices, triangles)
+    result = (vertices, triangles, u) if return_field else (vertices, triangles)
+    return result + (counts,) if return_counts else result
 
 
 def write_ply(path, vertices, triangles):

@@ -98,7 +98,10 @@ ENTRY_POINTS_DATA = ("pvd_image_batch", "pvd_error_map_update")
 ENTRY_POINTS_MARCH = ("pvd_occ_coarse_mask", "pvd_march_rays_train_mask")
 # ... and the triangle-mesh extraction of include/pvd_hip_mesh.h (tests/test_abi_mesh.py)
 ENTRY_POINTS_MESH = ("pvd_mesh_workspace_bytes", "pvd_mesh_count", "pvd_mesh_emit")
-for _name in ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH:
+# ... and the connected components of a density volume's inside set, include/pvd_hip_components.h (tests/test_abi_components.py)
+ENTRY_POINTS_COMPONENTS = ("pvd_components_label", "pvd_components_filter", "pvd_components_neighbours")
+for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
+              + ENTRY_POINTS_COMPONENTS):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
@@ -1563,3 +1566,49 @@ raymarching_backend = types.SimpleNamespace(
 )
 gridencoder_backend = types.SimpleNamespace(grid_encode_forward=grid_encode_forward, grid_encode_backward=grid_encode_backward)
 shencoder_backend = types.SimpleNamespace(sh_encode_forward=sh_encode_forward, sh_encode_backward=sh_encode_backward)
+
+
+# --------------------------------------------------------------------------- connected components (include/pvd_hip_components.h)
+def _components_common(field, R, labels, sizes, stats):
+    _want(field, torch.float32, "field"), _want(labels, torch.int32, "labels"), _want(sizes, torch.int32, "sizes")
+    _want(stats, torch.int32, "stats")
+    R = int(R)
+    if not 2 <= R <= MESH_MAX_R:
+        raise PvdHipError("R must be 2 .. %d, got %d" % (MESH_MAX_R, R))
+    if field.numel() != R ** 3 or labels.numel() != R ** 3 or sizes.numel() != R ** 3:
+        raise PvdHipError("field, labels and sizes must hold R^3 values each")
+    if stats.numel() < 4:
+        raise PvdHipError("stats must hold 4 int32 values")
+    return R
+
+
+def components_label(field, R, thresh, labels, sizes, stats):
+    """pvd_components_label: labels int32 [R^3] <- the smallest linear index of the point's component of the set field > thresh
+    (14-neighbour Kuhn connectivity), -1 outside; sizes int32 [R^3] <- the component's points at its label, 0 elsewhere; stats
+    int32 [4] <- (components, inside points, size of the largest component, its label).  All on the device."""
+    dev = _dev(field, labels, sizes, stats)
+    R = _components_common(field, R, labels, sizes, stats)
+    _call("pvd_components_label", dev, _p(field), _u32(R), _f32(thresh), _p(labels), _p(sizes), _p(stats))
+
+
+def components_filter(field, labels, sizes, stats, R, thresh, min_points, largest_only, out, kept):
+    """pvd_components_filter: out <- field with the points of dropped components set to thresh (dropped: size < min_points, or
+    largest_only and not the largest); labels, sizes, stats as components_label left them; out may be field itself; kept int32 [2]
+    <- (components kept, points kept), on the device."""
+    dev = _dev(field, labels, sizes, stats, out, kept)
+    R = _components_common(field, R, labels, sizes, stats)
+    _want(out, torch.float32, "out"), _want(kept, torch.int32, "kept")
+    if out.numel() != R ** 3 or kept.numel() < 2:
+        raise PvdHipError("out must hold R^3 floats and kept 2 int32 values")
+    if not 0 <= int(min_points) < 2 ** 32:
+        raise PvdHipError("min_points must fit 32 unsigned bits")
+    _call("pvd_components_filter", dev, _p(field), _p(labels), _p(sizes), _p(stats), _u32(R), _f32(thresh), _u32(min_points),
+          _u32(1 if largest_only else 0), _p(out), _p(kept))
+
+
+def components_neighbours():
+    """pvd_components_neighbours: the 14 offsets of the connectivity, a list of (dx, dy, dz)."""
+    buf = (ctypes.c_int32 * 42)()
+    n = int(_lib.pvd_components_neighbours(buf))
+    _check(min(n, 0), "pvd_components_neighbours")
+    return [tuple(buf[3 * q:3 * q + 3]) for q in range(n)]

@@ -4,9 +4,12 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
 
   python tools/train_distill.py --save-student student.pth [--save-teacher teacher.pth]
   python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
+                              [--min-component N] [--largest-only]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
-The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean)."""
+The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
+--min-component N drops the connected components of the inside set with fewer than N lattice points ("floaters"), --largest-only
+all but the largest one, before meshing (csrc/components.hip); the components found and kept are printed."""
 import argparse
 import os
 import sys
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--threshold", type=float, default=None)
     ap.add_argument("--resolution0", type=int, default=PVDConfig.resolution0, help="VM: initial resolution (the file's own is loaded)")
     ap.add_argument("--plenoxel-res", default=PVDConfig.plenoxel_res)
+    ap.add_argument("--min-component", type=int, default=0, help="drop components of fewer lattice points before meshing")
+    ap.add_argument("--largest-only", action="store_true", help="keep the largest component only")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     opt = PVDConfig(model_type=a.model_type, resolution0=a.resolution0, plenoxel_res=a.plenoxel_res)
@@ -41,10 +46,17 @@ def main():
         print("state-dict keys missing %s, unexpected %s" % (missing, unexpected), file=sys.stderr)
     model.eval()
     thresh = default_threshold(model) if a.threshold is None else a.threshold
-    vertices, triangles = extract_geometry(model, resolution=a.resolution, threshold=thresh)
+    filtering = a.min_component > 0 or a.largest_only
+    if filtering:
+        vertices, triangles, counts = extract_geometry(model, resolution=a.resolution, threshold=thresh, min_points=a.min_component,
+                                                       largest_only=a.largest_only, return_counts=True)
+    else:
+        vertices, triangles = extract_geometry(model, resolution=a.resolution, threshold=thresh)
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
     write_ply(out, vertices, triangles)
     print("%s: %d vertices, %d triangles at density %.6g, resolution %d" % (out, vertices.shape[0], triangles.shape[0], thresh, a.resolution))
+    if filtering:
+        print("components: %d found, %d kept, %d points kept" % counts)
 
 
 if __name__ == "__main__":
