@@ -12,11 +12,14 @@
 //                 -> the point's first vertex index and first triangle index.
 // k_mesh_emit     one lane per lattice point: the owned vertices (world positions) and the owned cell's triangles; a triangle
 //                 finds a vertex another point owns from that point's mask and first vertex index.
+// k_mesh_normals  (include/pvd_hip_mesh_attr.h) one lane per lattice point: the normal of every owned vertex, from the gradient of
+//                 the field at the two ends of its edge; reads the mask and the first vertex index the passes above left.
 // Reduce-then-scan in separate launches: no workgroup waits on another one of the same launch, nothing is atomic, and the
 // output does not depend on the order in which workgroups run.
 #include "pvd_device.h"
 
 #include "../../include/pvd_hip_mesh.h"
+#include "../../include/pvd_hip_mesh_attr.h"
 
 namespace {
 
@@ -309,6 +312,67 @@ __global__ __launch_bounds__(kThreads) void k_mesh_emit(const float *__restrict_
     }
 }
 
+// world gradient of u at the lattice point q = (c[0], c[1], c[2]) (include/pvd_hip_mesh_attr.h): central differences inside the
+// lattice, one-sided ones on its faces, each scaled by the axis' lattice points per world unit
+__device__ __forceinline__ void world_gradient(const float *__restrict__ u, uint32_t R, uint32_t q, const uint32_t c[3], const float inv_h[3],
+                                               float g[3]) {
+    const uint32_t stride[3] = {R * R, R, 1u};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float d;
+        if (c[a] == 0)
+            d = u[q + stride[a]] - u[q];
+        else if (c[a] == R - 1)
+            d = u[q] - u[q - stride[a]];
+        else
+            d = (u[q + stride[a]] - u[q - stride[a]]) * 0.5f;
+        g[a] = d * inv_h[a];
+    }
+}
+
+// one lane per lattice point, as k_mesh_emit: the normals of the vertices this point owns, in slot order, to the rows voff[n] ...
+// A wave's points are consecutive along k, so its stencil loads are consecutive floats of 5 rows for the owner and of the rows
+// one step further for the other endpoints; they overlap between neighbouring lanes and slots and are served by L1 / L2.
+__global__ __launch_bounds__(kThreads) void k_mesh_normals(const float *__restrict__ u, uint32_t R, uint32_t N, float thresh,
+                                                          const float *__restrict__ bmin3, const float *__restrict__ bmax3,
+                                                          const uint8_t *__restrict__ vmask, const uint32_t *__restrict__ voff,
+                                                          float *__restrict__ normals, uint32_t V) {
+    const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t mask = vmask[n];
+    if (!mask) return;
+    const uint32_t i = n / (R * R), r = n - i * R * R, j = r / R, k = r - j * R;
+    const float rm1 = (float)(R - 1);
+    const float inv_h[3] = {rm1 / (bmax3[0] - bmin3[0]), rm1 / (bmax3[1] - bmin3[1]), rm1 / (bmax3[2] - bmin3[2])};
+    const uint32_t ca[3] = {i, j, k};
+    const float ua = u[n];
+    float ga[3];
+    world_gradient(u, R, n, ca, inv_h, ga);
+    uint32_t at = voff[n];
+#pragma unroll
+    for (uint32_t s = 0; s < 7; ++s) {
+        if ((mask >> s) & 1u) {
+            if (at < V) {
+                const uint32_t d = dcode_of(s), ox = d >> 2, oy = (d >> 1) & 1u, oz = d & 1u;
+                const uint32_t b = n + (ox * R + oy) * R + oz;  // a lattice point: the count pass sets a slot only where it is one
+                const uint32_t cb[3] = {i + ox, j + oy, k + oz};
+                float gb[3];
+                world_gradient(u, R, b, cb, inv_h, gb);
+                const float ub = u[b];
+                const float t = (thresh - ua) / (ub - ua);
+                const float gx = ga[0] + t * (gb[0] - ga[0]), gy = ga[1] + t * (gb[1] - ga[1]), gz = ga[2] + t * (gb[2] - ga[2]);
+                const float len = sqrtf(gx * gx + gy * gy + gz * gz);
+                const bool ok = len > 0.0f && len < INFINITY;  // false for NaN
+                float *o = normals + 3 * (size_t)at;
+                o[0] = ok ? -gx / len : 0.0f;
+                o[1] = ok ? -gy / len : 0.0f;
+                o[2] = ok ? -gz / len : 0.0f;
+            }
+            ++at;
+        }
+    }
+}
+
 int check_args(const void *field, uint32_t R, const void *workspace, size_t workspace_bytes) {
     if (!field || !workspace || ((uintptr_t)workspace & 3u)) return PVD_ERR_INVALID;
     if (R < 2 || R > PVD_MESH_MAX_R) return PVD_ERR_UNSUPPORTED;
@@ -355,6 +419,21 @@ int pvd_mesh_emit(const float *field, uint32_t R, float thresh, const float *bmi
     hipLaunchKernelGGL(k_mesh_emit, dim3(NB), dim3(kThreads), 0, (hipStream_t)stream, field, R, N, thresh, bmin3, bmax3,
                        (const uint8_t *)(ws + l.vmask), (const uint32_t *)(ws + l.voff), (const uint32_t *)(ws + l.toff), vertices, V,
                        triangles, T);
+    return check_launch();
+}
+
+int pvd_mesh_normals(const float *field, uint32_t R, float thresh, const float *bmin3, const float *bmax3, const void *workspace,
+                     size_t workspace_bytes, float *normals, uint32_t V, pvd_stream_t stream) {
+    if (!bmin3 || !bmax3) return PVD_ERR_INVALID;
+    const int rc = check_args(field, R, workspace, workspace_bytes);
+    if (rc != PVD_OK) return rc;
+    if (V == 0) return PVD_OK;
+    if (!normals) return PVD_ERR_INVALID;
+    const Layout l = layout(R);
+    const uint32_t N = R * R * R, NB = div_up(N, kThreads);
+    const char *ws = (const char *)workspace;
+    hipLaunchKernelGGL(k_mesh_normals, dim3(NB), dim3(kThreads), 0, (hipStream_t)stream, field, R, N, thresh, bmin3, bmax3,
+                       (const uint8_t *)(ws + l.vmask), (const uint32_t *)(ws + l.voff), normals, V);
     return check_launch();
 }
 

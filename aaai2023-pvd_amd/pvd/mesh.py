@@ -41,9 +41,11 @@ def density_field(query, R, bmin, bmax, chunk=1 << 21, device=None):
     return u
 
 
-def extract_mesh(field, thresh, bmin, bmax):
+def extract_mesh(field, thresh, bmin, bmax, with_normals=False):
     """(vertices [V,3] f32, triangles [T,3] int32), device tensors, of the surface field = thresh (inside: field > thresh; normals
-    point outwards); field [R,R,R] f32 on the device, vertices in the box bmin .. bmax.  One read-back: the two totals."""
+    point outwards); field [R,R,R] f32 on the device, vertices in the box bmin .. bmax.  One read-back: the two totals.
+    with_normals=True: (vertices, triangles, normals [V,3] f32) -- the outward unit normal of every vertex from the gradient of the
+    field (include/pvd_hip_mesh_attr.h), one more launch on the same workspace; (0,0,0) where the gradient is zero or not finite."""
     import pvd_hip
     if field.dim() != 3 or field.shape[0] != field.shape[1] or field.shape[0] != field.shape[2]:
         raise ValueError("field must be [R,R,R]")
@@ -57,7 +59,11 @@ def extract_mesh(field, thresh, bmin, bmax):
     vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
     triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
     pvd_hip.mesh_emit(field, R, float(thresh), lo, hi, ws, vertices, triangles)
-    return vertices, triangles
+    if not with_normals:
+        return vertices, triangles
+    normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    pvd_hip.mesh_normals(field, R, float(thresh), lo, hi, ws, normals)
+    return vertices, triangles, normals
 
 
 def _cube(field):
@@ -139,18 +145,88 @@ def extract_geometry(model, resolution=256, threshold=None, bmin=None, bmax=None
     return result + (counts,) if return_counts else result
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY: float x y z per vertex, (uchar 3, int a b c) per face."""
+@torch.no_grad()
+def vertex_colors(model, vertices, normals, chunk=1 << 20, autocast=True):
+    """[V,3] f32 in [0,1] on the device: the colour head of `model` at every vertex, seen straight on -- rgb = model(x, d)[1] with
+    d = -normal, `chunk` rows at a time, under fp16 autocast as evaluate_views renders (autocast=False: f32).  A vertex whose
+    normal is (0,0,0) is looked at along (0,0,-1).  A vertex whose position or normal is not finite never reaches the model -- the
+    centre of model.aabb_infer is evaluated in its place -- and gets the colour 0."""
+    V = int(vertices.shape[0])
+    out = torch.empty(V, 3, dtype=torch.float32, device=vertices.device)
+    if V == 0:
+        return out
+    aabb = model.aabb_infer.to(device=vertices.device, dtype=torch.float32)
+    centre = (aabb[:3] + aabb[3:]) * 0.5
+    down = torch.tensor([0.0, 0.0, -1.0], device=vertices.device)
+    for s in range(0, V, int(chunk)):
+        x, n = vertices[s:s + int(chunk)].to(torch.float32), normals[s:s + int(chunk)].to(torch.float32)
+        bad = ~(torch.isfinite(x).all(dim=1) & torch.isfinite(n).all(dim=1))
+        flat = bad | (n == 0).all(dim=1)
+        x = torch.where(bad[:, None], centre[None, :], x).contiguous()
+        d = torch.where(flat[:, None], down[None, :], -n).contiguous()
+        with torch.autocast("cuda", dtype=torch.float16, enabled=bool(autocast)):
+            rgb = model(x, d)[1]
+        out[s:s + x.shape[0]] = torch.where(bad[:, None], torch.zeros_like(x), rgb.to(torch.float32).clamp(0.0, 1.0))
+    return out
+
+
+def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, min_points=0, largest_only=False,
+                    normals=True, colors=True):
+    """extract_geometry with what a viewer needs next to the geometry, as a dict: vertices, triangles, normals (extract_mesh's
+    with_normals) and colors (vertex_colors), None where not asked for; field (the density volume, filtered where min_points > 0
+    or largest_only), threshold, and counts = (components found, components kept, points kept), None where nothing was filtered.
+    Colours are taken along the normals: colors=True with normals=False computes them and returns normals=None."""
+    aabb = model.aabb_infer
+    lo = aabb[:3] if bmin is None else bmin
+    hi = aabb[3:] if bmax is None else bmax
+    if threshold is None:
+        threshold = default_threshold(model)
+    u = density_field(lambda x: model.density(x)["sigma"], resolution, lo, hi, chunk=chunk, device=aabb.device)
+    counts = None
+    if int(min_points) > 0 or largest_only:
+        stats, kept = _drop(u, int(resolution), threshold, min_points, largest_only, u)
+        counts = (int(stats[0]),) + tuple(int(v) for v in kept.tolist())
+    nrm = col = None
+    if normals or colors:
+        vertices, triangles, nrm = extract_mesh(u, threshold, lo, hi, with_normals=True)
+        if colors:
+            col = vertex_colors(model, vertices, nrm)
+    else:
+        vertices, triangles = extract_mesh(u, threshold, lo, hi)
+    return dict(vertices=vertices, triangles=triangles, normals=nrm if normals else None, colors=col, field=u,
+                threshold=float(threshold), counts=counts)
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None):
+    """Binary little-endian PLY: float x y z per vertex, (uchar 3, int a b c) per face.  normals [V,3]: float nx ny nz after z;
+    colors [V,3] in [0,1]: uchar red green blue after those, round(clamp(c, 0, 1) * 255)."""
     import numpy as np
-    v = np.ascontiguousarray(vertices.detach().cpu().numpy() if torch.is_tensor(vertices) else vertices, dtype="<f4").reshape(-1, 3)
-    t = np.ascontiguousarray(triangles.detach().cpu().numpy() if torch.is_tensor(triangles) else triangles, dtype="<i4").reshape(-1, 3)
+
+    def host(a, dtype):
+        return np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=dtype).reshape(-1, 3)
+    v, t = host(vertices, "<f4"), host(triangles, "<i4")
     faces = np.empty(len(t), dtype=[("n", "u1"), ("v", "<i4", (3,))])
     faces["n"] = 3
     faces["v"] = t
-    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-              "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(t)))
+    fields, props = [("p", "<f4", (3,))], "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        fields.append(("n", "<f4", (3,)))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        fields.append(("c", "u1", (3,)))
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    rows = np.empty(len(v), dtype=fields)  # packed: 12, 24, 15 or 27 bytes per vertex
+    rows["p"] = v
+    if normals is not None:
+        rows["n"] = host(normals, "<f4")
+    if colors is not None:
+        c = host(colors, "<f4")
+        with np.errstate(invalid="ignore"):
+            rows["c"] = np.rint(np.clip(np.nan_to_num(c, nan=0.0), 0.0, 1.0) * 255.0).astype("u1")
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%selement face %d\nproperty list uchar int vertex_indices\n"
+              "end_header\n" % (len(v), props, len(t)))
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
-        f.write(v.tobytes())
+        f.write(rows.tobytes())
         f.write(faces.tobytes())
     return path

@@ -100,8 +100,10 @@ ENTRY_POINTS_MARCH = ("pvd_occ_coarse_mask", "pvd_march_rays_train_mask")
 ENTRY_POINTS_MESH = ("pvd_mesh_workspace_bytes", "pvd_mesh_count", "pvd_mesh_emit")
 # ... and the connected components of a density volume's inside set, include/pvd_hip_components.h (tests/test_abi_components.py)
 ENTRY_POINTS_COMPONENTS = ("pvd_components_label", "pvd_components_filter", "pvd_components_neighbours")
+# ... and the per-vertex attributes of that mesh, include/pvd_hip_mesh_attr.h (tests/test_abi_mesh_attr.py)
+ENTRY_POINTS_MESH_ATTR = ("pvd_mesh_normals",)
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
-              + ENTRY_POINTS_COMPONENTS):
+              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
@@ -1549,6 +1551,20 @@ def mesh_emit(field, R, thresh, bmin, bmax, workspace, vertices, triangles):
     V, T = vertices.numel() // 3, triangles.numel() // 3
     _call("pvd_mesh_emit", dev, _p(field), _u32(R), _f32(thresh), _p(bmin), _p(bmax), _p(workspace), ctypes.c_size_t(workspace.numel()),
           _p(vertices), _u32(V), _p(triangles), _u32(T))
+
+
+def mesh_normals(field, R, thresh, bmin, bmax, workspace, normals):
+    """pvd_mesh_normals (include/pvd_hip_mesh_attr.h): normals [V,3] f32 <- the outward unit normal of every vertex mesh_emit writes,
+    from the gradient of the SAME field (R, thresh, box and workspace as for mesh_emit); V == 0: nothing is launched."""
+    dev = _dev(field, workspace, bmin, bmax, normals)
+    R = _mesh_common(field, R, workspace)
+    _f32_all(bmin=bmin, bmax=bmax, normals=normals)
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    if normals.numel() % 3:
+        raise PvdHipError("normals must be [V,3]")
+    _call("pvd_mesh_normals", dev, _p(field), _u32(R), _f32(thresh), _p(bmin), _p(bmax), _p(workspace), ctypes.c_size_t(workspace.numel()),
+          _p(normals), _u32(normals.numel() // 3))
 
 
 raymarching_backend = types.SimpleNamespace(

@@ -4,12 +4,14 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
 
   python tools/train_distill.py --save-student student.pth [--save-teacher teacher.pth]
   python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
-                              [--min-component N] [--largest-only]
+                              [--min-component N] [--largest-only] [--normals] [--colors]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
 The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
 --min-component N drops the connected components of the inside set with fewer than N lattice points ("floaters"), --largest-only
-all but the largest one, before meshing (csrc/components.hip); the components found and kept are printed."""
+all but the largest one, before meshing (csrc/components.hip); the components found and kept are printed.
+--normals adds a smooth unit normal per vertex (nx ny nz: the gradient of the density volume, pvd_mesh_normals), --colors the
+model's own colour at the vertex, seen along the normal (red green blue; it computes the normals whether or not they are written)."""
 import argparse
 import os
 import sys
@@ -21,7 +23,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
 
 from pvd.checkpoint import load_student_checkpoint  # noqa: E402
 from pvd.config import PVDConfig  # noqa: E402
-from pvd.mesh import default_threshold, extract_geometry, write_ply  # noqa: E402
+from pvd.mesh import default_threshold, extract_surface, write_ply  # noqa: E402
 from pvd.ops import hip_ops  # noqa: E402
 from pvd.workload import make_model  # noqa: E402
 
@@ -37,6 +39,8 @@ def main():
     ap.add_argument("--plenoxel-res", default=PVDConfig.plenoxel_res)
     ap.add_argument("--min-component", type=int, default=0, help="drop components of fewer lattice points before meshing")
     ap.add_argument("--largest-only", action="store_true", help="keep the largest component only")
+    ap.add_argument("--normals", action="store_true", help="write a unit normal per vertex (nx ny nz)")
+    ap.add_argument("--colors", action="store_true", help="write the model's colour per vertex (red green blue)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     opt = PVDConfig(model_type=a.model_type, resolution0=a.resolution0, plenoxel_res=a.plenoxel_res)
@@ -47,16 +51,15 @@ def main():
     model.eval()
     thresh = default_threshold(model) if a.threshold is None else a.threshold
     filtering = a.min_component > 0 or a.largest_only
-    if filtering:
-        vertices, triangles, counts = extract_geometry(model, resolution=a.resolution, threshold=thresh, min_points=a.min_component,
-                                                       largest_only=a.largest_only, return_counts=True)
-    else:
-        vertices, triangles = extract_geometry(model, resolution=a.resolution, threshold=thresh)
+    m = extract_surface(model, resolution=a.resolution, threshold=thresh, min_points=a.min_component, largest_only=a.largest_only,
+                        normals=a.normals, colors=a.colors)
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
-    write_ply(out, vertices, triangles)
-    print("%s: %d vertices, %d triangles at density %.6g, resolution %d" % (out, vertices.shape[0], triangles.shape[0], thresh, a.resolution))
+    write_ply(out, m["vertices"], m["triangles"], normals=m["normals"], colors=m["colors"])
+    carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
+    print("%s: %d vertices (%s), %d triangles at density %.6g, resolution %d"
+          % (out, m["vertices"].shape[0], carries, m["triangles"].shape[0], thresh, a.resolution))
     if filtering:
-        print("components: %d found, %d kept, %d points kept" % counts)
+        print("components: %d found, %d kept, %d points kept" % m["counts"])
 
 
 if __name__ == "__main__":
