@@ -230,3 +230,143 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
         f.write(rows.tobytes())
         f.write(faces.tobytes())
     return path
+
+
+def read_ply(path):
+    """(vertices [V,3] f32, triangles [T,3] int32, normals [V,3] f32 | None, colors [V,3] f32 in [0,1] | None) of a file write_ply
+    wrote, in any of its four vertex layouts, as host tensors; colours come back as byte / 255."""
+    import numpy as np
+    kinds = {"float": "<f4", "uchar": "u1"}
+    with open(path, "rb") as f:
+        if f.readline() != b"ply\n" or f.readline() != b"format binary_little_endian 1.0\n":
+            raise ValueError("%s: not a binary little-endian PLY" % path)
+        counts, fields, element = {}, [], None
+        for line in iter(f.readline, b"end_header\n"):
+            words = line.decode("ascii").split()
+            if not words:
+                raise ValueError("%s: the header does not end" % path)
+            if words[0] == "element":
+                element = words[1]
+                counts[element] = int(words[2])
+            elif words[0] == "property" and element == "vertex" and words[1] in kinds:
+                fields.append((words[2], kinds[words[1]]))
+            elif line != b"property list uchar int vertex_indices\n":
+                raise ValueError("%s: unexpected header line %r" % (path, line))
+        rows = np.frombuffer(f.read(np.dtype(fields).itemsize * counts["vertex"]), np.dtype(fields))
+        faces = np.frombuffer(f.read(13 * counts["face"]), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    if len(rows) != counts["vertex"] or len(faces) != counts["face"] or not np.all(faces["n"] == 3):
+        raise ValueError("%s: truncated, or a face that is not a triangle" % path)
+
+    def columns(names, scale=None):
+        if not all(n in rows.dtype.names for n in names):
+            return None
+        a = np.stack([rows[n] for n in names], axis=1).astype(np.float32)
+        return torch.from_numpy(a / np.float32(scale) if scale else a)
+    return (columns(("x", "y", "z")), torch.from_numpy(np.array(faces["v"], np.int32)), columns(("nx", "ny", "nz")),
+            columns(("red", "green", "blue"), 255.0))
+
+
+def default_grid(T):
+    """Cells per axis mesh_distance uses for a mesh of T triangles: round(sqrt(T / 8)), clamped to 1 .. 256.  An extracted surface
+    of T triangles crosses about T / 5 cells of its lattice (R ~ sqrt(T / 5) per axis), so this keeps a cell near 1.3 lattice
+    spacings and rho near one cell: rings 0 .. 2 decide a query close to the surface.  profiles/mesh_dist.txt has the timings."""
+    return max(1, min(256, int(round((max(int(T), 0) / 8.0) ** 0.5))))
+
+
+def _finite_box(vertices):
+    """Bounding box of the finite vertices, (lo, hi) f32 [3] on the device; the unit box where there is none."""
+    ok = torch.isfinite(vertices).all(dim=1, keepdim=True)
+    inf = torch.tensor(float("inf"), device=vertices.device)
+    lo = torch.where(ok, vertices, inf).amin(dim=0) if vertices.shape[0] else inf.expand(3)
+    hi = torch.where(ok, vertices, -inf).amax(dim=0) if vertices.shape[0] else -inf.expand(3)
+    none = ~torch.isfinite(lo) | ~torch.isfinite(hi)
+    return torch.where(none, torch.zeros_like(lo), lo).contiguous(), torch.where(none, torch.ones_like(hi), hi).contiguous()
+
+
+def mesh_distance(points, vertices, triangles, max_dist, bmin=None, bmax=None, grid=None):
+    """(dist [N] f32, tri [N] int32), device tensors: the distance from every row of points [N,3] to the mesh (vertices [V,3] f32,
+    triangles [T,3] int32) and the index of the nearest triangle, exact in float64 and rounded once (include/pvd_hip_mesh_dist.h;
+    csrc/mesh_dist.hip).  (max_dist, -1) where nothing is nearer than max_dist (finite, > 0) -- max_dist bounds the work per point --
+    and (NaN, -1) for a point that is not finite.  Triangles with an index outside [0, V) or a corner that is not finite are
+    ignored.  The grid of grid^3 cells (default: default_grid(T)) lies over bmin .. bmax (default: the bounding box of the finite
+    vertices); neither changes a bit of the result, only the time."""
+    import pvd_hip
+    dev = vertices.device
+    points = points.to(torch.float32).reshape(-1, 3).contiguous()
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    T = int(triangles.shape[0])
+    G = default_grid(T) if grid is None else max(1, min(pvd_hip.MESH_DIST_MAX_G, int(grid)))
+    box = _finite_box(vertices) if bmin is None or bmax is None else None
+    lo = box[0] if bmin is None else _box(bmin, bmin, dev)[0]
+    hi = box[1] if bmax is None else _box(bmax, bmax, dev)[0]
+    ws = torch.empty(pvd_hip.mesh_dist_workspace_bytes(T, G), dtype=torch.uint8, device=dev)
+    pvd_hip.mesh_dist_build(vertices, triangles, lo, hi, G, ws)
+    dist = torch.empty(points.shape[0], dtype=torch.float32, device=dev)
+    tri = torch.empty(points.shape[0], dtype=torch.int32, device=dev)
+    pvd_hip.mesh_dist_query(points, T, G, ws, float(max_dist), dist, tri)
+    return dist, tri
+
+
+def sample_surface(vertices, triangles, n, seed):
+    """points [n,3] f32 on the device, uniform over the surface: a triangle is drawn with probability proportional to its area
+    (cumulative sum + searchsorted), a point in it by square-root barycentrics; a seeded device generator, so the same seed gives
+    the same bits.  Invalid triangles and triangles of area 0 get no samples; a mesh without area gives an empty tensor."""
+    dev = vertices.device
+    v, t = vertices.to(torch.float32).reshape(-1, 3), triangles.to(torch.int64).reshape(-1, 3)
+    if v.shape[0] == 0:
+        return torch.empty(0, 3, dtype=torch.float32, device=dev)
+    ok = ((t >= 0) & (t < v.shape[0])).all(dim=1)
+    corners = v[torch.where(ok[:, None], t, torch.zeros_like(t))].to(torch.float64)  # [T,3,3]
+    ok &= torch.isfinite(corners).all(dim=2).all(dim=1)
+    area = torch.linalg.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0]).norm(dim=1) * 0.5
+    area = torch.where(ok & torch.isfinite(area), area, torch.zeros_like(area))
+    cum = torch.cumsum(area, dim=0)
+    if int(n) <= 0 or cum.numel() == 0 or not float(cum[-1]) > 0.0:
+        return torch.empty(0, 3, dtype=torch.float32, device=dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    u = torch.rand(int(n), 3, dtype=torch.float64, device=dev, generator=gen)
+    # the first triangle whose cumulative area exceeds the draw: never one of area 0 (its cumulative value equals its predecessor's)
+    pick = torch.searchsorted(cum, u[:, 0] * cum[-1], right=True).clamp(max=cum.numel() - 1)
+    pick = torch.where(area[pick] > 0, pick, torch.argmax(area).expand_as(pick))  # (a draw of exactly the total)
+    s = torch.sqrt(u[:, 1])
+    w = torch.stack([1.0 - s, s * (1.0 - u[:, 2]), s * u[:, 2]], dim=1)  # [n,3]
+    return (w[:, :, None] * corners[pick]).sum(dim=1).to(torch.float32)
+
+
+def compare_meshes(va, ta, vb, tb, tau, max_dist=None, samples=0, seed=0):
+    """How far apart two meshes are, as a dict.  The points of a mesh are its vertices, or `samples` surface samples
+    (sample_surface; seeds `seed` for A and `seed + 1` for B) when samples > 0; every point of A is measured against mesh B and
+    the other way round (mesh_distance; max_dist defaults to the diagonal of the joint bounding box).
+        a_to_b, b_to_a   mean distance from A's points to B, from B's points to A
+        chamfer          their sum
+        hausdorff        the larger of the two largest distances
+        precision        share of A's points within tau of B;  recall: the same for B's points;  fscore: their harmonic mean
+        n_a, n_b         points measured;  saturated_a, saturated_b: those with no triangle within max_dist (or not finite)
+    Saturated rows count as max_dist in the means and the maxima and never as within tau; rows that are not finite are left out
+    of the means, the maxima and the shares' denominators.  The
+    reductions run in float64 on the device and come back in one read-back (the default max_dist costs one more)."""
+    dev = va.device
+    va, vb = va.to(torch.float32).reshape(-1, 3), vb.to(torch.float32).reshape(-1, 3)
+    if max_dist is None:
+        lo_a, hi_a = _finite_box(va)
+        lo_b, hi_b = _finite_box(vb)
+        diag = float((torch.maximum(hi_a, hi_b) - torch.minimum(lo_a, lo_b)).to(torch.float64).norm())
+        max_dist = diag if diag > 0.0 else 1.0
+    pa = sample_surface(va, ta, samples, seed) if int(samples) > 0 else va
+    pb = sample_surface(vb, tb, samples, int(seed) + 1) if int(samples) > 0 else vb
+
+    def one_side(points, v, t):
+        d, tri = mesh_distance(points, v, t, max_dist)
+        d = d.to(torch.float64)
+        ok = torch.isfinite(d)
+        n = ok.sum().to(torch.float64).clamp(min=1.0)
+        dz = torch.where(ok, d, torch.zeros_like(d))
+        return torch.stack([dz.sum() / n, dz.max() if d.numel() else dz.sum(), ((d <= float(tau)) & (tri >= 0)).sum() / n,
+                            (tri < 0).sum().to(torch.float64)])
+    both = torch.cat([one_side(pa, vb, tb), one_side(pb, va, ta)]).tolist()
+    (m_ab, h_ab, prec, sat_a), (m_ba, h_ba, rec, sat_b) = both[:4], both[4:]
+    return dict(a_to_b=m_ab, b_to_a=m_ba, chamfer=m_ab + m_ba, hausdorff=max(h_ab, h_ba), precision=prec, recall=rec,
+                fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0, n_a=int(pa.shape[0]), n_b=int(pb.shape[0]),
+                saturated_a=int(sat_a), saturated_b=int(sat_b))

@@ -102,12 +102,15 @@ ENTRY_POINTS_MESH = ("pvd_mesh_workspace_bytes", "pvd_mesh_count", "pvd_mesh_emi
 ENTRY_POINTS_COMPONENTS = ("pvd_components_label", "pvd_components_filter", "pvd_components_neighbours")
 # ... and the per-vertex attributes of that mesh, include/pvd_hip_mesh_attr.h (tests/test_abi_mesh_attr.py)
 ENTRY_POINTS_MESH_ATTR = ("pvd_mesh_normals",)
+# ... and the point-to-mesh distance of include/pvd_hip_mesh_dist.h (tests/test_abi_mesh_dist.py)
+ENTRY_POINTS_MESH_DIST = ("pvd_mesh_dist_workspace_bytes", "pvd_mesh_dist_build", "pvd_mesh_dist_query")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
-              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR):
+              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_dist_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -1628,3 +1631,61 @@ def components_neighbours():
     n = int(_lib.pvd_components_neighbours(buf))
     _check(min(n, 0), "pvd_components_neighbours")
     return [tuple(buf[3 * q:3 * q + 3]) for q in range(n)]
+
+
+# --------------------------------------------------------------------------- point-to-mesh distance (include/pvd_hip_mesh_dist.h)
+MESH_DIST_MAX_G = 256  # PVD_MESH_DIST_MAX_G: cells per axis, 1 .. 256
+
+
+def mesh_dist_workspace_bytes(T, G):
+    """pvd_mesh_dist_workspace_bytes: bytes of workspace mesh_dist_build / mesh_dist_query need for T triangles and G^3 cells."""
+    ok = 0 <= int(T) < 2 ** 32 and 0 <= int(G) < 2 ** 32
+    n = int(_lib.pvd_mesh_dist_workspace_bytes(_u32(T), _u32(G))) if ok else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_dist_workspace_bytes: G must be 1 .. %d and T below 2^31, got T=%d G=%d" % (MESH_DIST_MAX_G, int(T), int(G)))
+    return n
+
+
+def _mesh_dist_workspace(workspace, T, G):
+    _want(workspace, torch.uint8, "workspace")
+    if workspace.numel() < mesh_dist_workspace_bytes(T, G):
+        raise PvdHipError("workspace too small: mesh_dist_workspace_bytes(T, G) bytes are needed")
+    if workspace.data_ptr() % 16:
+        raise PvdHipError("workspace must be 16-byte aligned")
+
+
+def mesh_dist_build(vertices, triangles, bmin, bmax, G, workspace):
+    """pvd_mesh_dist_build: bins the valid triangles of the mesh (vertices [V,3] f32, triangles [T,3] int32) into G^3 cells over the
+    box bmin .. bmax (device f32 [3] each) and leaves in the workspace (uint8, mesh_dist_workspace_bytes(T, G)) what mesh_dist_query
+    needs."""
+    dev = _dev(vertices, triangles, bmin, bmax, workspace)
+    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
+    _want(triangles, torch.int32, "triangles")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    _mesh_dist_workspace(workspace, T, G)
+    _call("pvd_mesh_dist_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _p(workspace),
+          ctypes.c_size_t(workspace.numel()))
+
+
+def mesh_dist_query(points, T, G, workspace, max_dist, dist, tri):
+    """pvd_mesh_dist_query: dist [N] f32, tri [N] int32 <- the distance from every row of points [N,3] f32 to the mesh
+    mesh_dist_build left in the workspace for the SAME T and G, and the nearest triangle; (max_dist, -1) where nothing is nearer
+    than max_dist (finite, > 0), (NaN, -1) for a point that is not finite."""
+    dev = _dev(points, workspace, dist, tri)
+    _f32_all(points=points, dist=dist)
+    _want(tri, torch.int32, "tri")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise PvdHipError("points must be [N,3]")
+    N = int(points.shape[0])
+    if dist.numel() != N or tri.numel() != N:
+        raise PvdHipError("dist and tri must hold N values each")
+    max_dist = float(max_dist)
+    if not (0.0 < max_dist < float("inf")):
+        raise PvdHipError("max_dist must be finite and > 0")
+    _mesh_dist_workspace(workspace, T, G)
+    _call("pvd_mesh_dist_query", dev, _p(points), _u32(N), _u32(T), _u32(G), _p(workspace), ctypes.c_size_t(workspace.numel()),
+          _f32(max_dist), _p(dist), _p(tri))
