@@ -171,11 +171,13 @@ def vertex_colors(model, vertices, normals, chunk=1 << 20, autocast=True):
 
 
 def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, min_points=0, largest_only=False,
-                    normals=True, colors=True):
+                    normals=True, colors=True, simplify=0):
     """extract_geometry with what a viewer needs next to the geometry, as a dict: vertices, triangles, normals (extract_mesh's
     with_normals) and colors (vertex_colors), None where not asked for; field (the density volume, filtered where min_points > 0
     or largest_only), threshold, and counts = (components found, components kept, points kept), None where nothing was filtered.
-    Colours are taken along the normals: colors=True with normals=False computes them and returns normals=None."""
+    Colours are taken along the normals: colors=True with normals=False computes them and returns normals=None.
+    simplify=G > 0: the mesh, with the normals and colours asked for, goes through simplify_mesh with G cells per axis over the
+    extraction box; the dict then also holds vertex_map and full_counts = (vertices, triangles) before the simplification."""
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -193,8 +195,12 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
             col = vertex_colors(model, vertices, nrm)
     else:
         vertices, triangles = extract_mesh(u, threshold, lo, hi)
-    return dict(vertices=vertices, triangles=triangles, normals=nrm if normals else None, colors=col, field=u,
-                threshold=float(threshold), counts=counts)
+    out = dict(vertices=vertices, triangles=triangles, normals=nrm if normals else None, colors=col, field=u,
+               threshold=float(threshold), counts=counts)
+    if int(simplify) > 0:
+        small = simplify_mesh(vertices, triangles, int(simplify), bmin=lo, bmax=hi, normals=out["normals"], colors=col)
+        out.update(small, full_counts=(int(vertices.shape[0]), int(triangles.shape[0])))
+    return out
 
 
 def write_ply(path, vertices, triangles, normals=None, colors=None):
@@ -370,3 +376,44 @@ def compare_meshes(va, ta, vb, tb, tau, max_dist=None, samples=0, seed=0):
     return dict(a_to_b=m_ab, b_to_a=m_ba, chamfer=m_ab + m_ba, hausdorff=max(h_ab, h_ba), precision=prec, recall=rec,
                 fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0, n_a=int(pa.shape[0]), n_b=int(pb.shape[0]),
                 saturated_a=int(sat_a), saturated_b=int(sat_b))
+
+
+def simplify_mesh(vertices, triangles, grid, bmin=None, bmax=None, normals=None, colors=None):
+    """The mesh made smaller by vertex clustering on a grid of grid^3 cells (1 .. 512 per axis) over the box bmin .. bmax (default: the
+    bounding box of the finite vertices; vertices outside a given box are projected onto it), as a dict of device tensors: vertices
+    [V',3] f32 -- one per cell that a surviving triangle touches, the mean of the cell's vertices --, triangles [T',3] int32 -- those
+    whose corners lie in three different cells, in input order and orientation --, normals and colors (None where not given) -- the
+    cell means, normals renormalised ((0,0,0) where the mean is zero or not finite), colours clamped to [0,1] --, and vertex_map [V]
+    int32, the new index of every input vertex (-1: not finite, or in a cell no surviving triangle touches).  Every sum is an integer
+    sum: the result is bit-identical from run to run (include/pvd_hip_mesh_simplify.h; csrc/mesh_simplify.hip).  Duplicate output
+    triangles are not merged and the result is not guaranteed manifold.  No vertex that keeps an index moves further than one cell
+    (plus rounding) per axis.  One read-back: the two totals."""
+    import pvd_hip
+    dev = vertices.device
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    V, T, G = int(vertices.shape[0]), int(triangles.shape[0]), int(grid)
+    parts = [a.to(torch.float32).reshape(V, 3) for a in (normals, colors) if a is not None]
+    attrs = torch.cat(parts, dim=1).contiguous() if parts else None
+    K = 3 * len(parts)
+    box = _finite_box(vertices) if bmin is None or bmax is None else None
+    lo = box[0] if bmin is None else _box(bmin, bmin, dev)[0]
+    hi = box[1] if bmax is None else _box(bmax, bmax, dev)[0]
+    ws = torch.empty(pvd_hip.mesh_simplify_workspace_bytes(V, T, G, K), dtype=torch.uint8, device=dev)
+    totals = torch.zeros(2, dtype=torch.int32, device=dev)
+    pvd_hip.mesh_simplify_count(vertices, triangles, lo, hi, G, K, ws, totals)
+    Vn, Tn = (int(v) for v in totals.tolist())
+    out_v = torch.empty(Vn, 3, dtype=torch.float32, device=dev)
+    out_t = torch.empty(Tn, 3, dtype=torch.int32, device=dev)
+    out_a = torch.empty(Vn, K, dtype=torch.float32, device=dev) if K else None
+    vmap = torch.empty(V, dtype=torch.int32, device=dev)
+    pvd_hip.mesh_simplify_emit(vertices, triangles, attrs, lo, hi, G, ws, out_v, out_a, out_t, vmap)
+    nrm = col = None
+    if normals is not None:
+        mean = out_a[:, :3]
+        length = torch.linalg.norm(mean, dim=1, keepdim=True)
+        ok = torch.isfinite(length) & (length > 0)
+        nrm = torch.where(ok, mean / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(mean)).contiguous()
+    if colors is not None:
+        col = out_a[:, K - 3:].clamp(0.0, 1.0).contiguous()
+    return dict(vertices=out_v, triangles=out_t, normals=nrm, colors=col, vertex_map=vmap)

@@ -104,13 +104,16 @@ ENTRY_POINTS_COMPONENTS = ("pvd_components_label", "pvd_components_filter", "pvd
 ENTRY_POINTS_MESH_ATTR = ("pvd_mesh_normals",)
 # ... and the point-to-mesh distance of include/pvd_hip_mesh_dist.h (tests/test_abi_mesh_dist.py)
 ENTRY_POINTS_MESH_DIST = ("pvd_mesh_dist_workspace_bytes", "pvd_mesh_dist_build", "pvd_mesh_dist_query")
+# ... and the vertex clustering of include/pvd_hip_mesh_simplify.h (tests/test_abi_mesh_simplify.py)
+ENTRY_POINTS_MESH_SIMPLIFY = ("pvd_mesh_simplify_workspace_bytes", "pvd_mesh_simplify_count", "pvd_mesh_simplify_emit")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
-              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST):
+              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_dist_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_simplify_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -1689,3 +1692,77 @@ def mesh_dist_query(points, T, G, workspace, max_dist, dist, tri):
     _mesh_dist_workspace(workspace, T, G)
     _call("pvd_mesh_dist_query", dev, _p(points), _u32(N), _u32(T), _u32(G), _p(workspace), ctypes.c_size_t(workspace.numel()),
           _f32(max_dist), _p(dist), _p(tri))
+
+
+# --------------------------------------------------------------------------- vertex clustering (include/pvd_hip_mesh_simplify.h)
+MESH_SIMPLIFY_MAX_G = 512  # PVD_MESH_SIMPLIFY_MAX_G: cells per axis, 1 .. 512
+MESH_SIMPLIFY_MAX_K = 8  # PVD_MESH_SIMPLIFY_MAX_K: attributes per vertex, 0 .. 8
+
+
+def mesh_simplify_workspace_bytes(V, T, G, K):
+    """pvd_mesh_simplify_workspace_bytes: bytes of workspace mesh_simplify_count / mesh_simplify_emit need for V vertices, T
+    triangles, G^3 cells and K attributes per vertex."""
+    ok = all(0 <= int(x) < 2 ** 32 for x in (V, T, G, K))
+    n = int(_lib.pvd_mesh_simplify_workspace_bytes(_u32(V), _u32(T), _u32(G), _u32(K))) if ok else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_simplify_workspace_bytes: G must be 1 .. %d, K 0 .. %d, V and T below 2^31, got V=%d T=%d G=%d K=%d"
+                          % (MESH_SIMPLIFY_MAX_G, MESH_SIMPLIFY_MAX_K, int(V), int(T), int(G), int(K)))
+    return n
+
+
+def _mesh_simplify_common(vertices, triangles, bmin, bmax, G, K, workspace):
+    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
+    _want(triangles, torch.int32, "triangles"), _want(workspace, torch.uint8, "workspace")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    if workspace.numel() < mesh_simplify_workspace_bytes(V, T, G, K):
+        raise PvdHipError("workspace too small: mesh_simplify_workspace_bytes(V, T, G, K) bytes are needed")
+    if workspace.data_ptr() % 16:
+        raise PvdHipError("workspace must be 16-byte aligned")
+    return V, T
+
+
+def mesh_simplify_count(vertices, triangles, bmin, bmax, G, K, workspace, totals):
+    """pvd_mesh_simplify_count: the count phase of the vertex clustering of the mesh (vertices [V,3] f32, triangles [T,3] int32) over
+    G^3 cells of the box bmin .. bmax (device f32 [3] each); leaves the workspace (uint8, mesh_simplify_workspace_bytes(V, T, G, K)) as
+    mesh_simplify_emit needs it; totals int32 [2] <- (new vertices, surviving triangles), on the device."""
+    dev = _dev(vertices, triangles, bmin, bmax, workspace, totals)
+    V, T = _mesh_simplify_common(vertices, triangles, bmin, bmax, G, K, workspace)
+    _want(totals, torch.int32, "totals")
+    if totals.numel() < 2:
+        raise PvdHipError("totals must hold 2 int32 values")
+    _call("pvd_mesh_simplify_count", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _u32(K),
+          _p(workspace), ctypes.c_size_t(workspace.numel()), _p(totals))
+
+
+def mesh_simplify_emit(vertices, triangles, attrs, bmin, bmax, G, workspace, out_vertices, out_attrs, out_triangles, vertex_map):
+    """pvd_mesh_simplify_emit: out_vertices [V',3] f32, out_attrs [V',K] f32 (None with attrs None: K = 0), out_triangles [T',3]
+    int32 and vertex_map [V] int32 of the SAME mesh, box, G and the workspace mesh_simplify_count left; V' and T' are the totals it
+    wrote.  attrs [V,K] f32, K <= 8."""
+    dev = _dev(vertices, triangles, attrs, bmin, bmax, workspace, out_vertices, out_attrs, out_triangles, vertex_map)
+    if (attrs is None) != (out_attrs is None):
+        raise PvdHipError("attrs and out_attrs go together")
+    K = 0
+    if attrs is not None:
+        _f32_all(attrs=attrs, out_attrs=out_attrs)
+        if attrs.dim() != 2 or out_attrs.dim() != 2 or attrs.shape[1] != out_attrs.shape[1]:
+            raise PvdHipError("attrs must be [V,K] and out_attrs [V',K]")
+        K = int(attrs.shape[1])
+    V, T = _mesh_simplify_common(vertices, triangles, bmin, bmax, G, K, workspace)
+    _f32_all(out_vertices=out_vertices)
+    _want(out_triangles, torch.int32, "out_triangles"), _want(vertex_map, torch.int32, "vertex_map")
+    if out_vertices.dim() != 2 or out_vertices.shape[1] != 3 or out_triangles.dim() != 2 or out_triangles.shape[1] != 3:
+        raise PvdHipError("out_vertices must be [V',3] and out_triangles [T',3]")
+    Vn, Tn = int(out_vertices.shape[0]), int(out_triangles.shape[0])
+    if attrs is not None and (int(attrs.shape[0]) != V or int(out_attrs.shape[0]) != Vn):
+        raise PvdHipError("attrs must hold V rows and out_attrs V' rows")
+    if vertex_map.numel() != V:
+        raise PvdHipError("vertex_map must hold V values")
+    if Vn > min(V, int(G) ** 3) or Tn > T:
+        raise PvdHipError("V' is at most min(V, G^3) and T' at most T")
+    _call("pvd_mesh_simplify_emit", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(attrs if K else None), _u32(K), _p(bmin),
+          _p(bmax), _u32(G), _p(workspace), ctypes.c_size_t(workspace.numel()), _p(out_vertices), _u32(Vn), _p(out_attrs if K else None),
+          _p(out_triangles), _u32(Tn), _p(vertex_map))
