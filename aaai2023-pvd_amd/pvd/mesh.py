@@ -417,3 +417,117 @@ def simplify_mesh(vertices, triangles, grid, bmin=None, bmax=None, normals=None,
     if colors is not None:
         col = out_a[:, K - 3:].clamp(0.0, 1.0).contiguous()
     return dict(vertices=out_v, triangles=out_t, normals=nrm, colors=col, vertex_map=vmap)
+
+
+def mesh_raycast(origins, dirs, vertices, triangles, t_min=0.0, t_max=float("inf"), bmin=None, bmax=None, grid=None):
+    """(t [N] f32, tri [N] int32, bary [N,2] f32), device tensors: the first hit of every ray (origins [N,3], dirs [N,3]; dirs need not
+    be unit length, t is in units of |dir|) on the mesh (vertices [V,3] f32, triangles [T,3] int32) with t_min <= t < t_max -- the
+    watertight test in unfused float64, rounded once (include/pvd_hip_mesh_ray.h; csrc/mesh_ray.hip).  tri is the triangle, bary the
+    weights of its second and third corner.  (t_max, -1, (0, 0)) where nothing is hit, (NaN, -1, (0, 0)) for a ray that is not finite
+    or has a zero direction.  Triangles with an index outside [0, V) or a corner that is not finite are ignored.  The grid of grid^3
+    cells (default: default_grid(T); 1 .. 256, anything else raises) lies over bmin .. bmax (default: the bounding box of the finite
+    vertices); neither changes a bit of the result, only the time -- but for the edge-on case include/pvd_hip_mesh_ray.h names.  One
+    read-back: the two totals of the count pass."""
+    import pvd_hip
+    dev = vertices.device
+    origins = origins.to(torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(torch.float32).reshape(-1, 3).contiguous()
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    T = int(triangles.shape[0])
+    G = default_grid(T) if grid is None else int(grid)  # (a grid outside 1 .. 256 is an error of the binding's, not clamped)
+    lo, hi = _finite_box(vertices) if bmin is None or bmax is None else (None, None)
+    if bmin is not None:
+        lo = torch.as_tensor(bmin, dtype=torch.float32, device=dev).reshape(3).contiguous()
+    if bmax is not None:
+        hi = torch.as_tensor(bmax, dtype=torch.float32, device=dev).reshape(3).contiguous()
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    pvd_hip.mesh_ray_count(vertices, triangles, lo, hi, G, totals)
+    pairs = int(totals.tolist()[0])
+    ws = torch.empty(pvd_hip.mesh_ray_workspace_bytes(T, G, pairs), dtype=torch.uint8, device=dev)
+    pvd_hip.mesh_ray_build(vertices, triangles, lo, hi, G, pairs, ws)
+    N = int(origins.shape[0])
+    t = torch.empty(N, dtype=torch.float32, device=dev)
+    tri = torch.empty(N, dtype=torch.int32, device=dev)
+    bary = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    pvd_hip.mesh_ray_cast(origins, dirs, T, G, pairs, ws, float(t_min), float(t_max), t, tri, bary)
+    return t, tri, bary
+
+
+def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, colors=None, bg_color=1.0, grid=None):
+    """The mesh seen from the camera `pose` ([4,4] cam2world; rays from pvd.scene.get_rays, unit directions, so t is a distance), as
+    a dict of device tensors:
+        depth [H,W] f32     the distance to the first hit, 0 where nothing is hit
+        mask  [H,W] bool    hit or not;   tri [H,W] int32, bary [H,W,2] f32: mesh_raycast's
+        normal [H,W,3]      the barycentric mean of the vertex normals [V,3], renormalised, where they are given; otherwise the unit
+                            face normal turned towards the camera; (0,0,0) off the mesh (and where the mean or the face is null)
+        color [H,W,3]       the barycentric mean of the vertex colours [V,3] over bg_color (a float or 3 floats); None without colors
+    The interpolation is plain torch gathers on the cast's output."""
+    from .scene import get_rays
+    dev = vertices.device
+    pose = torch.as_tensor(pose, dtype=torch.float32, device=dev).reshape(4, 4)
+    r = get_rays(pose[None], intrinsics, int(H), int(W), -1)
+    o, d = r["rays_o"].reshape(-1, 3).contiguous(), r["rays_d"].reshape(-1, 3).contiguous()
+    t, tri, bary = mesh_raycast(o, d, vertices, triangles, grid=grid)
+    mask = tri >= 0
+    if int(triangles.shape[0]) == 0 or int(vertices.shape[0]) == 0:  # nothing to gather from: every pixel is background
+        col = None
+        if colors is not None:
+            col = torch.as_tensor(bg_color, dtype=torch.float32, device=dev).expand(H, W, 3).contiguous()
+        return dict(depth=torch.zeros(H, W, dtype=torch.float32, device=dev), mask=mask.reshape(H, W), tri=tri.reshape(H, W),
+                    bary=bary.reshape(H, W, 2), normal=torch.zeros(H, W, 3, dtype=torch.float32, device=dev), color=col)
+    idx = triangles.to(torch.int64).reshape(-1, 3)[tri.clamp(min=0).to(torch.int64)]  # [N,3]; row 0 stands in off the mesh
+    w = torch.stack([1.0 - bary[:, 0] - bary[:, 1], bary[:, 0], bary[:, 1]], dim=1)  # [N,3]
+    zero = torch.zeros(o.shape[0], 3, dtype=torch.float32, device=dev)
+
+    def mix(attr):
+        return (w[:, :, None] * attr.to(torch.float32).reshape(-1, 3)[idx]).sum(dim=1)
+
+    def unit(n):
+        length = torch.linalg.norm(n, dim=1, keepdim=True)
+        ok = torch.isfinite(length) & (length > 0)
+        return torch.where(ok, n / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(n))
+    if normals is not None:
+        nrm = unit(mix(normals))
+    else:
+        c = vertices.to(torch.float32).reshape(-1, 3)[idx]  # [N,3,3]
+        face = torch.linalg.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0])
+        nrm = unit(torch.where(((face * d).sum(dim=1, keepdim=True) > 0), -face, face))
+    nrm = torch.where(mask[:, None], nrm, zero)
+    col = None
+    if colors is not None:
+        bg = torch.as_tensor(bg_color, dtype=torch.float32, device=dev).expand(3)
+        col = torch.where(mask[:, None], mix(colors), bg[None, :]).reshape(H, W, 3)
+    return dict(depth=torch.where(mask, t, torch.zeros_like(t)).reshape(H, W), mask=mask.reshape(H, W), tri=tri.reshape(H, W),
+                bary=bary.reshape(H, W, 2), normal=nrm.reshape(H, W, 3), color=col)
+
+
+@torch.no_grad()
+def evaluate_mesh_views(vertices, triangles, colors, poses, intrinsics, H, W, truth, bg_color=1.0, grid=None, keep_images=False):
+    """Render the coloured mesh from poses [P,4,4] (render_mesh) and measure each view's colour image against `truth` the way
+    pvd.metrics.evaluate_views does for a model: a tensor [P,H,W,3], or a callable (rays_o, rays_d) -> [H*W,3].  Returns
+    ImageMeter.report() plus "coverage", the share of all pixels that hit the mesh (and, with keep_images, the views under
+    "images")."""
+    from .metrics import ImageMeter
+    from .scene import get_rays
+    meter = ImageMeter()
+    images, hit, pixels = [], None, 0
+    for v, pose in enumerate(poses):
+        pose = torch.as_tensor(pose, dtype=torch.float32, device=vertices.device).reshape(4, 4)
+        out = render_mesh(vertices, triangles, pose, intrinsics, H, W, colors=colors, bg_color=bg_color, grid=grid)
+        if callable(truth):
+            r = get_rays(pose[None], intrinsics, int(H), int(W), -1)
+            gt = truth(r["rays_o"], r["rays_d"])
+        else:
+            gt = truth[v]
+        meter.update(out["color"], gt.to(vertices.device).float().reshape(H, W, 3))
+        n = out["mask"].sum()
+        hit = n if hit is None else hit + n
+        pixels += int(H) * int(W)
+        if keep_images:
+            images.append(out["color"])
+    report = meter.report()
+    report["coverage"] = float(hit) / pixels if pixels else float("nan")
+    if keep_images:
+        report["images"] = images
+    return report

@@ -69,6 +69,7 @@ _lib.pvd_abi_version.restype = ctypes.c_int
 ABI_VERSION = int(_lib.pvd_abi_version())
 
 _u32, _f32, _int, _vp = ctypes.c_uint32, ctypes.c_float, ctypes.c_int, ctypes.c_void_p
+_u64 = ctypes.c_uint64
 
 PVD_F32, PVD_F16 = 0, 1
 
@@ -106,14 +107,17 @@ ENTRY_POINTS_MESH_ATTR = ("pvd_mesh_normals",)
 ENTRY_POINTS_MESH_DIST = ("pvd_mesh_dist_workspace_bytes", "pvd_mesh_dist_build", "pvd_mesh_dist_query")
 # ... and the vertex clustering of include/pvd_hip_mesh_simplify.h (tests/test_abi_mesh_simplify.py)
 ENTRY_POINTS_MESH_SIMPLIFY = ("pvd_mesh_simplify_workspace_bytes", "pvd_mesh_simplify_count", "pvd_mesh_simplify_emit")
+# ... and the ray casting of include/pvd_hip_mesh_ray.h (tests/test_abi_mesh_ray.py)
+ENTRY_POINTS_MESH_RAY = ("pvd_mesh_ray_workspace_bytes", "pvd_mesh_ray_count", "pvd_mesh_ray_build", "pvd_mesh_ray_cast")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
-              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY):
+              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_dist_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_simplify_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_ray_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -1766,3 +1770,80 @@ def mesh_simplify_emit(vertices, triangles, attrs, bmin, bmax, G, workspace, out
     _call("pvd_mesh_simplify_emit", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(attrs if K else None), _u32(K), _p(bmin),
           _p(bmax), _u32(G), _p(workspace), ctypes.c_size_t(workspace.numel()), _p(out_vertices), _u32(Vn), _p(out_attrs if K else None),
           _p(out_triangles), _u32(Tn), _p(vertex_map))
+
+
+# --------------------------------------------------------------------------- ray casting against a mesh (include/pvd_hip_mesh_ray.h)
+MESH_RAY_MAX_G = 256  # PVD_MESH_RAY_MAX_G: cells per axis, 1 .. 256
+
+
+def mesh_ray_workspace_bytes(T, G, pairs):
+    """pvd_mesh_ray_workspace_bytes: bytes of workspace mesh_ray_build / mesh_ray_cast need for T triangles, G^3 cells and `pairs`
+    (cell, triangle) pairs (the first total of mesh_ray_count)."""
+    ok = 0 <= int(T) < 2 ** 32 and 0 <= int(G) < 2 ** 32 and 0 <= int(pairs) < 2 ** 64
+    n = int(_lib.pvd_mesh_ray_workspace_bytes(_u32(T), _u32(G), _u64(pairs))) if ok else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_ray_workspace_bytes: G must be 1 .. %d, T and pairs below 2^31, got T=%d G=%d pairs=%d"
+                          % (MESH_RAY_MAX_G, int(T), int(G), int(pairs)))
+    return n
+
+
+def _mesh_ray_workspace(workspace, T, G, pairs):
+    _want(workspace, torch.uint8, "workspace")
+    if workspace.numel() < mesh_ray_workspace_bytes(T, G, pairs):
+        raise PvdHipError("workspace too small: mesh_ray_workspace_bytes(T, G, pairs) bytes are needed")
+    if workspace.data_ptr() % 16:
+        raise PvdHipError("workspace must be 16-byte aligned")
+
+
+def _mesh_ray_mesh(vertices, triangles, bmin, bmax, G):
+    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
+    _want(triangles, torch.int32, "triangles")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    if not 1 <= int(G) <= MESH_RAY_MAX_G:
+        raise PvdHipError("G must be 1 .. %d, got %d" % (MESH_RAY_MAX_G, int(G)))
+    return int(vertices.shape[0]), int(triangles.shape[0])
+
+
+def mesh_ray_count(vertices, triangles, bmin, bmax, G, totals):
+    """pvd_mesh_ray_count: totals int64 [2] on the device <- (the (cell, triangle) pairs, the outside triangles) of the mesh (vertices
+    [V,3] f32, triangles [T,3] int32) over G^3 cells of the box bmin .. bmax (device f32 [3] each)."""
+    dev = _dev(vertices, triangles, bmin, bmax, totals)
+    V, T = _mesh_ray_mesh(vertices, triangles, bmin, bmax, G)
+    _want(totals, torch.int64, "totals")
+    if totals.numel() < 2:
+        raise PvdHipError("totals must hold 2 int64 values")
+    _call("pvd_mesh_ray_count", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _p(totals))
+
+
+def mesh_ray_build(vertices, triangles, bmin, bmax, G, pairs, workspace):
+    """pvd_mesh_ray_build: bins the valid triangles of the SAME mesh, box and G as mesh_ray_count, with the `pairs` it left, and leaves
+    in the workspace (uint8, mesh_ray_workspace_bytes(T, G, pairs)) what mesh_ray_cast needs."""
+    dev = _dev(vertices, triangles, bmin, bmax, workspace)
+    V, T = _mesh_ray_mesh(vertices, triangles, bmin, bmax, G)
+    _mesh_ray_workspace(workspace, T, G, pairs)
+    _call("pvd_mesh_ray_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _u64(pairs), _p(workspace),
+          ctypes.c_size_t(workspace.numel()))
+
+
+def mesh_ray_cast(origins, dirs, T, G, pairs, workspace, t_min, t_max, t, tri, bary):
+    """pvd_mesh_ray_cast: t [N] f32, tri [N] int32, bary [N,2] f32 <- the first hit of every ray (origins [N,3] f32, dirs [N,3] f32) on
+    the mesh mesh_ray_build left in the workspace for the SAME T, G and pairs: t in units of |dir|, the triangle, the weights of its
+    second and third corner; (t_max, -1, (0, 0)) without a hit in [t_min, t_max), (NaN, -1, (0, 0)) for a ray that is not finite or
+    has a zero direction.  t_min finite and >= 0, t_max > t_min (inf allowed)."""
+    dev = _dev(origins, dirs, workspace, t, tri, bary)
+    _f32_all(origins=origins, dirs=dirs, t=t, bary=bary)
+    _want(tri, torch.int32, "tri")
+    if origins.dim() != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape:
+        raise PvdHipError("origins and dirs must be [N,3]")
+    N = int(origins.shape[0])
+    if t.numel() != N or tri.numel() != N or bary.numel() != 2 * N:
+        raise PvdHipError("t and tri must hold N values each and bary 2 N")
+    t_min, t_max = float(t_min), float(t_max)
+    if not (0.0 <= t_min < float("inf")) or not t_max > t_min:
+        raise PvdHipError("t_min must be finite and >= 0 and t_max > t_min")
+    _mesh_ray_workspace(workspace, T, G, pairs)
+    _call("pvd_mesh_ray_cast", dev, _p(origins), _p(dirs), _u32(N), _u32(T), _u32(G), _u64(pairs), _p(workspace),
+          ctypes.c_size_t(workspace.numel()), _f32(t_min), _f32(t_max), _p(t), _p(tri), _p(bary))

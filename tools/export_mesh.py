@@ -5,6 +5,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
   python tools/train_distill.py --save-student student.pth [--save-teacher teacher.pth]
   python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
                               [--min-component N] [--largest-only] [--normals] [--colors] [--simplify G [--simplify-report]]
+                              [--render-check N]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
 The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
@@ -15,7 +16,14 @@ model's own colour at the vertex, seen along the normal (red green blue; it comp
 --simplify G makes the mesh smaller by vertex clustering on G^3 cells of the box (csrc/mesh_simplify.hip; normals and colours are
 averaged with the positions; duplicate triangles are not merged and the result is not guaranteed manifold) and prints the vertices
 and triangles before and after; --simplify-report also measures the simplified mesh against the original (compare_meshes over the
-vertices: Hausdorff, Chamfer) and prints the result next to the cell diagonal, which bounds the former."""
+vertices: Hausdorff, Chamfer) and prints the result next to the cell diagonal, which bounds the former.
+--render-check N (needs --colors) renders the coloured mesh (pvd/mesh.py: render_mesh, csrc/mesh_ray.hip) and the model itself from N
+pose_spherical views at 200 x 200 and prints the PSNR and SSIM of the mesh's image against the model's volume render, and the mean
+absolute difference of the two depths over the pixels where both hit.  Both depths are distances along the ray in world units: the
+mesh's is the ray cast's t (unit directions); the model's render returns its composited depth normalised to the ray's interval in
+the inference box, clamp(depth - near, 0) / (far - near), and is brought back with near + depth * (far - near), near and far from the
+model's own slab test (aabb_infer, min_near).  The composited depth is the weight-summed sample distance, not divided by the
+opacity, so it falls short of the surface where the model is not opaque."""
 import argparse
 import os
 import sys
@@ -27,9 +35,40 @@ sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
 
 from pvd.checkpoint import load_student_checkpoint  # noqa: E402
 from pvd.config import PVDConfig  # noqa: E402
-from pvd.mesh import compare_meshes, default_threshold, extract_mesh, extract_surface, write_ply  # noqa: E402
+from pvd.mesh import compare_meshes, default_threshold, extract_mesh, extract_surface, render_mesh, write_ply  # noqa: E402
 from pvd.ops import hip_ops  # noqa: E402
 from pvd.workload import make_model  # noqa: E402
+
+
+@torch.no_grad()
+def render_check(model, m, views, res=200):
+    """(ImageMeter report of the mesh's colour image against the model's render, mean |depth difference| over the pixels both hit,
+    their number), over `views` pose_spherical cameras on a circle at the reference's radius and scale.  Depths in world units along
+    the ray: the model's normalised depth d is turned back into near + d (far - near) with the near / far of its own slab test."""
+    import numpy as np
+    from pvd.metrics import ImageMeter
+    from pvd.renderer import near_far_from_aabb_torch
+    from pvd.scene import BLENDER_INTRINSICS, get_rays, nerf_matrix_to_ngp, pose_spherical
+    intr = tuple(v * res / 800.0 for v in BLENDER_INTRINSICS)
+    dev = m["vertices"].device
+    meter, diff, both = ImageMeter(), torch.zeros((), dtype=torch.float64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
+    for q in range(views):
+        pose = torch.from_numpy(nerf_matrix_to_ngp(pose_spherical(-180.0 + 360.0 * q / views, -30.0, 4.0)).astype(np.float32)).to(dev)
+        mesh = render_mesh(m["vertices"], m["triangles"], pose, intr, res, res, colors=m["colors"], bg_color=1.0)
+        r = get_rays(pose[None], intr, res, res, -1)
+        with torch.autocast("cuda", dtype=torch.float16):
+            vol = model.render(r["rays_o"], r["rays_d"], staged=True, bg_color=1, perturb=False, max_steps=1024)
+        meter.update(mesh["color"], vol["image"].float().reshape(res, res, 3))
+        if vol.get("depth") is not None:
+            near, far = near_far_from_aabb_torch(r["rays_o"].reshape(-1, 3), r["rays_d"].reshape(-1, 3), model.aabb_infer.float(),
+                                                 float(model.min_near))
+            unit = vol["depth"].float().reshape(-1)
+            depth = (near + unit * (far - near)).reshape(res, res)
+            hit = mesh["mask"] & (unit > 0).reshape(res, res) & (far > near).reshape(res, res)
+            diff += torch.where(hit, (mesh["depth"] - depth).abs(), torch.zeros_like(depth)).double().sum()
+            both += hit.sum()
+    n = int(both)
+    return meter.report(), (float(diff) / n if n else float("nan")), n
 
 
 def main():
@@ -47,7 +86,11 @@ def main():
     ap.add_argument("--colors", action="store_true", help="write the model's colour per vertex (red green blue)")
     ap.add_argument("--simplify", type=int, default=0, metavar="G", help="cluster the vertices on G^3 cells of the box (1 .. 512)")
     ap.add_argument("--simplify-report", action="store_true", help="measure the simplified mesh against the original")
+    ap.add_argument("--render-check", type=int, default=0, metavar="N",
+                    help="render the coloured mesh and the model from N views and print PSNR, SSIM and the depth difference (needs --colors)")
     a = ap.parse_args()
+    if a.render_check > 0 and not a.colors:
+        ap.error("--render-check needs --colors")
     dev = torch.device("cuda:0")
     opt = PVDConfig(model_type=a.model_type, resolution0=a.resolution0, plenoxel_res=a.plenoxel_res)
     model = make_model(hip_ops(), opt, a.model_type, False, dev)
@@ -75,6 +118,10 @@ def main():
             diagonal = float((aabb[3:] - aabb[:3]).double().norm()) / a.simplify
             d = compare_meshes(full_v, full_t, m["vertices"], m["triangles"], tau=diagonal)
             print("simplified against original: hausdorff %.6g, chamfer %.6g, cell diagonal %.6g" % (d["hausdorff"], d["chamfer"], diagonal))
+    if a.render_check > 0:
+        rep, depth_diff, n = render_check(model, m, a.render_check)
+        print("render check, %d views at 200 x 200, mesh against the model's volume render: PSNR %.2f dB, SSIM %.4f, mean |depth difference| "
+              "%.5f (world units along the ray) over %d pixels both hit" % (a.render_check, rep["psnr"], rep["ssim"], depth_diff, n))
 
 
 if __name__ == "__main__":

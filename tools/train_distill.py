@@ -104,6 +104,18 @@ def main():
         tau = 2.0 * float((aabb[3:] - aabb[:3]).max()) / (a.geometry - 1)
         print("geometry R=%d, A = teacher (%d triangles), B = student (%d triangles), tau %.5f: %s"
               % (a.geometry, tt.shape[0], ts.shape[0], tau, json.dumps(compare_meshes(vt, tt, vs, ts, tau))), flush=True)
+        # the student's coloured mesh, ray cast from the held-out views (csrc/mesh_ray.hip), scored like the student itself
+        from pvd.mesh import evaluate_mesh_views, extract_surface
+        res = 200
+        intr = tuple(v * res / 800.0 for v in BLENDER_INTRINSICS)
+        surf = extract_surface(w.stu.eval(), resolution=a.geometry)
+        w.stu.train()
+        white = torch.ones(1, res * res, 3, device=dev)
+        rep = evaluate_mesh_views(surf["vertices"], surf["triangles"], surf["colors"], held_out, intr, res, res,
+                                  lambda o, d: w.target(o, d, white))
+        _, sg, _ = evaluate(w, held_out, res)
+        print("student's coloured mesh vs GT on the held-out views: PSNR %.2f dB, SSIM %.4f, %.1f %% of the pixels hit "
+              "(the student's own render: %.2f dB / %.4f)" % (rep["psnr"], rep["ssim"], 100.0 * rep["coverage"], sg[0], sg[1]), flush=True)
 
 
 if __name__ == "__main__":
