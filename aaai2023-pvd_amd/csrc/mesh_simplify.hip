@@ -16,7 +16,7 @@
 // k_ms_remap     one lane per triangle: a survivor writes its remapped row at its rank.
 // The same count -> one-block scan -> offsets shape as csrc/mesh.hip and csrc/mesh_dist.hip: no workgroup waits on another one of
 // the same launch, and no loop retries an atomic.
-#include "pvd_device.h"
+#include "mesh_quant.h"
 
 #include "../../include/pvd_hip_mesh_simplify.h"
 
@@ -58,33 +58,7 @@ inline bool in_limits(uint32_t V, uint32_t T, uint32_t G, uint32_t K) {
     return G >= 1 && G <= PVD_MESH_SIMPLIFY_MAX_G && K <= (uint32_t)kMaxK && V <= kMaxN && T <= kMaxN;
 }
 
-// the pure parts are __host__ __device__: a CPU build can walk the same code
-#define PVD_HD __host__ __device__ __forceinline__
-
-PVD_HD bool finite1(float x) { return fabsf(x) < INFINITY; }  // false for NaN
-
-struct Box {  // per axis: the origin, the extent, whether the axis is flat
-    double lo[3], ext[3];
-    bool flat[3];
-};
-
-PVD_HD Box box_of(const float *__restrict__ bmin3, const float *__restrict__ bmax3) {
-    Box b;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        b.lo[a] = (double)bmin3[a];
-        b.ext[a] = (double)bmax3[a] - b.lo[a];
-        b.flat[a] = !(b.ext[a] > 0.0 && b.ext[a] < (double)INFINITY);  // NaN: flat
-    }
-    return b;
-}
-
-// q_a of a finite coordinate: 0 .. 2^30
-PVD_HD int64_t quantise(const Box &b, int a, float x) {
-    if (b.flat[a]) return 0;
-    const double f = fmin(1.0, fmax(0.0, ((double)x - b.lo[a]) / b.ext[a]));
-    return (int64_t)llrint(f * 0x1p30);
-}
+// finite1, Box, box_of and quantise (q_a) are in mesh_quant.h
 
 PVD_HD uint32_t cell_axis(int64_t q, uint32_t G) {
     const uint32_t k = (uint32_t)(((uint64_t)q * G) >> 30);

@@ -171,13 +171,16 @@ def vertex_colors(model, vertices, normals, chunk=1 << 20, autocast=True):
 
 
 def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, min_points=0, largest_only=False,
-                    normals=True, colors=True, simplify=0):
+                    normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
     """extract_geometry with what a viewer needs next to the geometry, as a dict: vertices, triangles, normals (extract_mesh's
     with_normals) and colors (vertex_colors), None where not asked for; field (the density volume, filtered where min_points > 0
     or largest_only), threshold, and counts = (components found, components kept, points kept), None where nothing was filtered.
     Colours are taken along the normals: colors=True with normals=False computes them and returns normals=None.
     simplify=G > 0: the mesh, with the normals and colours asked for, goes through simplify_mesh with G cells per axis over the
-    extraction box; the dict then also holds vertex_map and full_counts = (vertices, triangles) before the simplification."""
+    extraction box; the dict then also holds vertex_map and full_counts = (vertices, triangles) before the simplification.
+    smooth=N > 0: N iterations of smooth_mesh (weights smooth_lambda, smooth_mu) over the extraction box, after the colours -- which
+    are evaluated at the unsmoothed vertices, on the level set -- and before the simplification; the normals asked for are then
+    face_vertex_normals of the smoothed mesh, and the dict also holds smoothed = N.  smooth=0: the dict is what it was."""
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -195,8 +198,14 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
             col = vertex_colors(model, vertices, nrm)
     else:
         vertices, triangles = extract_mesh(u, threshold, lo, hi)
+    if int(smooth) > 0:
+        vertices = smooth_mesh(vertices, triangles, iterations=int(smooth), lam=smooth_lambda, mu=smooth_mu, bmin=lo, bmax=hi)
+        if normals:
+            nrm = face_vertex_normals(vertices, triangles)
     out = dict(vertices=vertices, triangles=triangles, normals=nrm if normals else None, colors=col, field=u,
                threshold=float(threshold), counts=counts)
+    if int(smooth) > 0:
+        out["smoothed"] = int(smooth)
     if int(simplify) > 0:
         small = simplify_mesh(vertices, triangles, int(simplify), bmin=lo, bmax=hi, normals=out["normals"], colors=col)
         out.update(small, full_counts=(int(vertices.shape[0]), int(triangles.shape[0])))
@@ -417,6 +426,61 @@ def simplify_mesh(vertices, triangles, grid, bmin=None, bmax=None, normals=None,
     if colors is not None:
         col = out_a[:, K - 3:].clamp(0.0, 1.0).contiguous()
     return dict(vertices=out_v, triangles=out_t, normals=nrm, colors=col, vertex_map=vmap)
+
+
+def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, bmin=None, bmax=None, pinned=None, return_totals=False):
+    """[V,3] f32 on the device: the vertices after `iterations` iterations of Taubin's lambda|mu filter -- a Laplacian pass with weight
+    lam > 0, then one with weight mu < -lam, which takes out the noise at the scale of an edge without the shrinkage of plain Laplacian
+    smoothing (mu=0 gives that).  Weighting: a pass moves every vertex by its weight towards the mean of the other corners of its
+    triangles, so a neighbour counts once per triangle shared with it -- the uniform umbrella on a closed manifold mesh, half weight
+    across a boundary edge.  Vertices of no valid triangle, vertices that are not finite and those with a non-zero byte in pinned [V]
+    keep their input bits; triangles with an index outside [0, V), a corner that is not finite or a repeated index are ignored.  The
+    topology and the triangle order are untouched: the triangles go with the result as they are.  The positions live on a 2^30
+    lattice of the box bmin .. bmax (default: the bounding box of the finite vertices; vertices outside a given box are projected onto
+    it) and every sum is an integer sum: the result is bit-identical from run to run (include/pvd_hip_mesh_smooth.h;
+    csrc/mesh_smooth.hip).  iterations <= 0 returns a copy without a launch.  No read-back; return_totals=True returns (vertices,
+    totals) with totals int64 [2] on the device: (row entries, largest row)."""
+    import pvd_hip
+    dev = vertices.device
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    if int(iterations) <= 0 or V == 0:
+        return (vertices.clone(), totals) if return_totals else vertices.clone()
+    box = _finite_box(vertices) if bmin is None or bmax is None else None
+    lo = box[0] if bmin is None else _box(bmin, bmin, dev)[0]
+    hi = box[1] if bmax is None else _box(bmax, bmax, dev)[0]
+    if pinned is not None:
+        pinned = (pinned.reshape(-1) != 0).to(torch.uint8).contiguous()
+    ws = torch.empty(pvd_hip.mesh_smooth_workspace_bytes(V, T), dtype=torch.uint8, device=dev)
+    pvd_hip.mesh_smooth_build(vertices, triangles, lo, hi, pinned, ws, totals)
+    out = torch.empty_like(vertices)
+    pvd_hip.mesh_smooth_run(vertices, T, lo, hi, ws, float(lam), float(mu), int(iterations), out)
+    return (out, totals) if return_totals else out
+
+
+def face_vertex_normals(vertices, triangles):
+    """[V,3] f32 unit normals from the faces: the sum of the area-weighted normals (half the cross products) of a vertex's triangles,
+    renormalised; (0,0,0) where the sum is null or not finite.  Plain torch (index_add_ of floats): NOT bit-reproducible from run to
+    run.  For meshes whose vertices were moved (smooth_mesh): the density-gradient normals of extract_mesh belong to the positions on
+    the level set.  Triangles with an index outside [0, V) are ignored."""
+    v = vertices.to(torch.float32).reshape(-1, 3)
+    t = triangles.to(torch.int64).reshape(-1, 3)
+    V = int(v.shape[0])
+    acc = torch.zeros(V, 3, dtype=torch.float32, device=v.device)
+    if V == 0 or int(t.shape[0]) == 0:
+        return acc
+    ok = ((t >= 0) & (t < V)).all(dim=1)
+    t = t[ok]
+    c = v[t]  # [T,3,3]
+    face = torch.linalg.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0]) * 0.5
+    face = torch.where(torch.isfinite(face).all(dim=1, keepdim=True), face, torch.zeros_like(face))
+    for k in range(3):
+        acc.index_add_(0, t[:, k], face)
+    length = torch.linalg.norm(acc, dim=1, keepdim=True)
+    good = torch.isfinite(length) & (length > 0)
+    return torch.where(good, acc / torch.where(good, length, torch.ones_like(length)), torch.zeros_like(acc)).contiguous()
 
 
 def mesh_raycast(origins, dirs, vertices, triangles, t_min=0.0, t_max=float("inf"), bmin=None, bmax=None, grid=None):

@@ -109,8 +109,11 @@ ENTRY_POINTS_MESH_DIST = ("pvd_mesh_dist_workspace_bytes", "pvd_mesh_dist_build"
 ENTRY_POINTS_MESH_SIMPLIFY = ("pvd_mesh_simplify_workspace_bytes", "pvd_mesh_simplify_count", "pvd_mesh_simplify_emit")
 # ... and the ray casting of include/pvd_hip_mesh_ray.h (tests/test_abi_mesh_ray.py)
 ENTRY_POINTS_MESH_RAY = ("pvd_mesh_ray_workspace_bytes", "pvd_mesh_ray_count", "pvd_mesh_ray_build", "pvd_mesh_ray_cast")
+# ... and the Taubin smoothing of include/pvd_hip_mesh_smooth.h (tests/test_abi_mesh_smooth.py)
+ENTRY_POINTS_MESH_SMOOTH = ("pvd_mesh_smooth_workspace_bytes", "pvd_mesh_smooth_build", "pvd_mesh_smooth_run")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
-              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY):
+              + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
+              + ENTRY_POINTS_MESH_SMOOTH):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
@@ -118,6 +121,7 @@ _lib.pvd_mesh_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_dist_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_simplify_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_ray_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_smooth_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -1847,3 +1851,70 @@ def mesh_ray_cast(origins, dirs, T, G, pairs, workspace, t_min, t_max, t, tri, b
     _mesh_ray_workspace(workspace, T, G, pairs)
     _call("pvd_mesh_ray_cast", dev, _p(origins), _p(dirs), _u32(N), _u32(T), _u32(G), _u64(pairs), _p(workspace),
           ctypes.c_size_t(workspace.numel()), _f32(t_min), _f32(t_max), _p(t), _p(tri), _p(bary))
+
+
+# --------------------------------------------------------------------------- Taubin smoothing (include/pvd_hip_mesh_smooth.h)
+MESH_SMOOTH_MAX_ITERATIONS = 1024  # PVD_MESH_SMOOTH_MAX_ITERATIONS
+
+
+def mesh_smooth_workspace_bytes(V, T):
+    """pvd_mesh_smooth_workspace_bytes: bytes of workspace mesh_smooth_build / mesh_smooth_run need for V vertices and T triangles."""
+    ok = all(0 <= int(x) < 2 ** 32 for x in (V, T))
+    n = int(_lib.pvd_mesh_smooth_workspace_bytes(_u32(V), _u32(T))) if ok else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_smooth_workspace_bytes: V and T must be below 2^31, got V=%d T=%d" % (int(V), int(T)))
+    return n
+
+
+def _mesh_smooth_common(vertices, T, bmin, bmax, workspace):
+    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
+    _want(workspace, torch.uint8, "workspace")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise PvdHipError("vertices must be [V,3]")
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    V = int(vertices.shape[0])
+    if workspace.numel() < mesh_smooth_workspace_bytes(V, T):
+        raise PvdHipError("workspace too small: mesh_smooth_workspace_bytes(V, T) bytes are needed")
+    if workspace.data_ptr() % 16:
+        raise PvdHipError("workspace must be 16-byte aligned")
+    return V
+
+
+def mesh_smooth_build(vertices, triangles, bmin, bmax, pinned, workspace, totals):
+    """pvd_mesh_smooth_build: quantises the mesh (vertices [V,3] f32, triangles [T,3] int32) in the box bmin .. bmax (device f32 [3]
+    each) and builds every vertex's row of neighbours in the workspace (uint8, mesh_smooth_workspace_bytes(V, T)) as mesh_smooth_run
+    needs it; pinned: [V] uint8 (not 0: the vertex does not move) or None; totals int64 [2] <- (row entries, largest row), on the
+    device."""
+    dev = _dev(vertices, triangles, bmin, bmax, pinned, workspace, totals)
+    _want(triangles, torch.int32, "triangles")
+    if triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise PvdHipError("triangles must be [T,3]")
+    T = int(triangles.shape[0])
+    V = _mesh_smooth_common(vertices, T, bmin, bmax, workspace)
+    if pinned is not None:
+        _want(pinned, torch.uint8, "pinned")
+        if pinned.numel() != V:
+            raise PvdHipError("pinned must hold V bytes")
+    _want(totals, torch.int64, "totals")
+    if totals.numel() < 2:
+        raise PvdHipError("totals must hold 2 int64 values")
+    _call("pvd_mesh_smooth_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _p(pinned), _p(workspace),
+          ctypes.c_size_t(workspace.numel()), _p(totals))
+
+
+def mesh_smooth_run(vertices, T, bmin, bmax, workspace, lam, mu, iterations, out_vertices):
+    """pvd_mesh_smooth_run: out_vertices [V,3] f32 <- the SAME vertices, T, box and the workspace mesh_smooth_build left after
+    `iterations` iterations (0 .. 1024) of a pass with weight lam and a pass with weight mu (finite, at most 1 in magnitude)."""
+    dev = _dev(vertices, bmin, bmax, workspace, out_vertices)
+    V = _mesh_smooth_common(vertices, T, bmin, bmax, workspace)
+    _f32_all(out_vertices=out_vertices)
+    if out_vertices.shape != vertices.shape:
+        raise PvdHipError("out_vertices must be [V,3]")
+    lam, mu, iterations = float(lam), float(mu), int(iterations)
+    if not (-1.0 <= lam <= 1.0 and -1.0 <= mu <= 1.0):
+        raise PvdHipError("lam and mu must be finite and at most 1 in magnitude")
+    if not 0 <= iterations <= MESH_SMOOTH_MAX_ITERATIONS:
+        raise PvdHipError("iterations must be 0 .. %d, got %d" % (MESH_SMOOTH_MAX_ITERATIONS, iterations))
+    _call("pvd_mesh_smooth_run", dev, _p(vertices), _u32(V), _u32(T), _p(bmin), _p(bmax), _p(workspace), ctypes.c_size_t(workspace.numel()),
+          ctypes.c_double(lam), ctypes.c_double(mu), _u32(iterations), _p(out_vertices))

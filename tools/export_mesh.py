@@ -5,7 +5,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
   python tools/train_distill.py --save-student student.pth [--save-teacher teacher.pth]
   python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
                               [--min-component N] [--largest-only] [--normals] [--colors] [--simplify G [--simplify-report]]
-                              [--render-check N]
+                              [--smooth N [--smooth-lambda L --smooth-mu M] [--smooth-report]] [--render-check N]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
 The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
@@ -17,6 +17,11 @@ model's own colour at the vertex, seen along the normal (red green blue; it comp
 averaged with the positions; duplicate triangles are not merged and the result is not guaranteed manifold) and prints the vertices
 and triangles before and after; --simplify-report also measures the simplified mesh against the original (compare_meshes over the
 vertices: Hausdorff, Chamfer) and prints the result next to the cell diagonal, which bounds the former.
+--smooth N runs N iterations of Taubin's lambda|mu filter over the vertices before any simplification (pvd/mesh.py: smooth_mesh,
+csrc/mesh_smooth.hip; weights --smooth-lambda 0.5 and --smooth-mu -0.53): the staircase of the lattice goes, the triangles stay as
+they are, the colours are those of the unsmoothed vertices and the normals written are recomputed from the faces.  --smooth-report
+prints two lines: the Hausdorff and Chamfer distance of the smoothed mesh to the unsmoothed one (compare_meshes over the vertices)
+next to the lattice spacing, and the volume the mesh encloses before and after (signed tetrahedra, float64).
 --render-check N (needs --colors) renders the coloured mesh (pvd/mesh.py: render_mesh, csrc/mesh_ray.hip) and the model itself from N
 pose_spherical views at 200 x 200 and prints the PSNR and SSIM of the mesh's image against the model's volume render, and the mean
 absolute difference of the two depths over the pixels where both hit.  Both depths are distances along the ray in world units: the
@@ -35,7 +40,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
 
 from pvd.checkpoint import load_student_checkpoint  # noqa: E402
 from pvd.config import PVDConfig  # noqa: E402
-from pvd.mesh import compare_meshes, default_threshold, extract_mesh, extract_surface, render_mesh, write_ply  # noqa: E402
+from pvd.mesh import compare_meshes, default_threshold, extract_mesh, extract_surface, render_mesh, smooth_mesh, write_ply  # noqa: E402
 from pvd.ops import hip_ops  # noqa: E402
 from pvd.workload import make_model  # noqa: E402
 
@@ -71,6 +76,12 @@ def render_check(model, m, views, res=200):
     return meter.report(), (float(diff) / n if n else float("nan")), n
 
 
+def enclosed_volume(vertices, triangles):
+    """The volume a closed mesh encloses: the sum of the signed tetrahedra (origin, a, b, c), float64 in torch."""
+    c = vertices.to(torch.float64)[triangles.to(torch.int64)]  # [T,3,3]
+    return float((c[:, 0] * torch.linalg.cross(c[:, 1], c[:, 2])).sum() / 6.0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoint")
@@ -86,6 +97,10 @@ def main():
     ap.add_argument("--colors", action="store_true", help="write the model's colour per vertex (red green blue)")
     ap.add_argument("--simplify", type=int, default=0, metavar="G", help="cluster the vertices on G^3 cells of the box (1 .. 512)")
     ap.add_argument("--simplify-report", action="store_true", help="measure the simplified mesh against the original")
+    ap.add_argument("--smooth", type=int, default=0, metavar="N", help="Taubin iterations over the vertices (0 .. 1024)")
+    ap.add_argument("--smooth-lambda", type=float, default=0.5)
+    ap.add_argument("--smooth-mu", type=float, default=-0.53)
+    ap.add_argument("--smooth-report", action="store_true", help="measure the smoothed mesh against the unsmoothed one")
     ap.add_argument("--render-check", type=int, default=0, metavar="N",
                     help="render the coloured mesh and the model from N views and print PSNR, SSIM and the depth difference (needs --colors)")
     a = ap.parse_args()
@@ -101,7 +116,8 @@ def main():
     thresh = default_threshold(model) if a.threshold is None else a.threshold
     filtering = a.min_component > 0 or a.largest_only
     m = extract_surface(model, resolution=a.resolution, threshold=thresh, min_points=a.min_component, largest_only=a.largest_only,
-                        normals=a.normals, colors=a.colors, simplify=a.simplify)
+                        normals=a.normals, colors=a.colors, simplify=a.simplify, smooth=a.smooth, smooth_lambda=a.smooth_lambda,
+                        smooth_mu=a.smooth_mu)
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
     write_ply(out, m["vertices"], m["triangles"], normals=m["normals"], colors=m["colors"])
     carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
@@ -109,6 +125,17 @@ def main():
           % (out, m["vertices"].shape[0], carries, m["triangles"].shape[0], thresh, a.resolution))
     if filtering:
         print("components: %d found, %d kept, %d points kept" % m["counts"])
+    if a.smooth > 0:
+        print("smooth: %d iterations, lambda %g, mu %g" % (a.smooth, a.smooth_lambda, a.smooth_mu))
+        if a.smooth_report:
+            aabb = model.aabb_infer
+            raw_v, raw_t = extract_mesh(m["field"], thresh, aabb[:3], aabb[3:])
+            new_v = smooth_mesh(raw_v, raw_t, iterations=a.smooth, lam=a.smooth_lambda, mu=a.smooth_mu, bmin=aabb[:3], bmax=aabb[3:])
+            spacing = float((aabb[3:] - aabb[:3]).double().max()) / (a.resolution - 1)
+            d = compare_meshes(raw_v, raw_t, new_v, raw_t, tau=spacing)
+            print("smoothed against unsmoothed: hausdorff %.6g, chamfer %.6g, lattice spacing %.6g" % (d["hausdorff"], d["chamfer"], spacing))
+            before, after = enclosed_volume(raw_v, raw_t), enclosed_volume(new_v, raw_t)
+            print("enclosed volume: %.6g before, %.6g after (%+.3f %%)" % (before, after, 100.0 * (after - before) / before if before else 0.0))
     if a.simplify > 0:
         print("simplify G=%d: %d -> %d vertices, %d -> %d triangles"
               % (a.simplify, m["full_counts"][0], m["vertices"].shape[0], m["full_counts"][1], m["triangles"].shape[0]))
