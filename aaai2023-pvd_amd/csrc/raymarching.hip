@@ -6,7 +6,7 @@
 // per-ray global atomics, and a deterministic prefix-sum slot allocator.
 #include "dda.h"
 #include "rays.h"
-#include "../../include/pvd_hip_march.h"
+#include "../../include/pvd_hip_prefix.h"
 
 #include <float.h>
 
@@ -60,6 +60,27 @@ __global__ void __launch_bounds__(kBlock) k_get_rays(const float *__restrict__ p
 // N random pixels of one pose and a random background colour per ray, utils.py:354, 987-995; then run_cuda's
 // near_far_from_aabb): pose = poses[state[0]], pixel ids and background from a PCG32 stream keyed by (seed, batch
 // counter, ray), rays, near/far.  The last workgroup to finish advances state = {pose index, batch counter, done}.
+__device__ __forceinline__ void make_batch_ray(const float *__restrict__ poses, long long pose_idx, long long batch, uint64_t seed, float fx,
+                                               float fy, float cx, float cy, uint32_t H, uint32_t W, uint32_t n,
+                                               const float *__restrict__ aabb, float min_near, int64_t *__restrict__ inds,
+                                               float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ bg,
+                                               float *__restrict__ nears, float *__restrict__ fars) {
+    Pcg32 g;
+    g.seed(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(batch + 1));
+    g.advance(4ull * n);
+    const int64_t k = (int64_t)(((uint64_t)g.next() * (uint64_t)(H * W)) >> 32);  // uniform in [0, H*W)
+    float o[3], d[3];
+    ray_of_pixel(poses + 16 * (size_t)pose_idx, fx, fy, cx, cy, k, W, o, d);
+    if (inds) inds[n] = k;
+#pragma unroll
+    for (int r = 0; r < 3; r++) { rays_o[3 * (size_t)n + r] = o[r]; rays_d[3 * (size_t)n + r] = d[r]; }
+    if (bg) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) bg[3 * (size_t)n + r] = g.next_float();
+    }
+    near_far_of(o, d, aabb, min_near, nears[n], fars[n]);
+}
+
 __global__ void __launch_bounds__(kBlock) k_make_ray_batch(const float *__restrict__ poses, uint32_t P, long long *__restrict__ state,
                                                            uint64_t seed, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                                                            uint32_t N, const float *__restrict__ aabb, float min_near,
@@ -68,22 +89,7 @@ __global__ void __launch_bounds__(kBlock) k_make_ray_batch(const float *__restri
                                                            float *__restrict__ fars) {
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     const long long pose_idx = state[0], batch = state[1];
-    if (n < N) {
-        Pcg32 g;
-        g.seed(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(batch + 1));
-        g.advance(4ull * n);
-        const int64_t k = (int64_t)(((uint64_t)g.next() * (uint64_t)(H * W)) >> 32);  // uniform in [0, H*W)
-        float o[3], d[3];
-        ray_of_pixel(poses + 16 * (size_t)pose_idx, fx, fy, cx, cy, k, W, o, d);
-        if (inds) inds[n] = k;
-#pragma unroll
-        for (int r = 0; r < 3; r++) { rays_o[3 * (size_t)n + r] = o[r]; rays_d[3 * (size_t)n + r] = d[r]; }
-        if (bg) {
-#pragma unroll
-            for (int r = 0; r < 3; r++) bg[3 * (size_t)n + r] = g.next_float();
-        }
-        near_far_of(o, d, aabb, min_near, nears[n], fars[n]);
-    }
+    if (n < N) make_batch_ray(poses, pose_idx, batch, seed, fx, fy, cx, cy, H, W, n, aabb, min_near, inds, rays_o, rays_d, bg, nears, fars);
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
@@ -91,6 +97,33 @@ __global__ void __launch_bounds__(kBlock) k_make_ray_batch(const float *__restri
         if (done == gridDim.x - 1) {  // every workgroup has read the state
             state[0] = (pose_idx + 1) % (long long)P;
             state[1] = batch + 1;
+            state[2] = 0;
+        }
+    }
+}
+
+// G consecutive batches in one launch (pvd_make_ray_batch_group): blockIdx.y = j is the batch the j-th of G single launches
+// would make -- pose (state[0] + j) % P, batch counter state[1] + j -- written to slice j of [G][N ...] outputs; the last
+// workgroup of the whole grid leaves the state G single launches leave.
+__global__ void __launch_bounds__(kBlock) k_make_ray_batch_group(const float *__restrict__ poses, uint32_t P, long long *__restrict__ state,
+                                                                 uint64_t seed, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                                                                 uint32_t N, const float *__restrict__ aabb, float min_near,
+                                                                 int64_t *__restrict__ inds, float *__restrict__ rays_o,
+                                                                 float *__restrict__ rays_d, float *__restrict__ bg, float *__restrict__ nears,
+                                                                 float *__restrict__ fars) {
+    const uint32_t n = blockIdx.x * kBlock + threadIdx.x, j = blockIdx.y, G = gridDim.y;
+    const long long pose0 = state[0], batch0 = state[1];
+    const size_t base = (size_t)j * N;
+    if (n < N)
+        make_batch_ray(poses, (pose0 + (long long)j) % (long long)P, batch0 + (long long)j, seed, fx, fy, cx, cy, H, W, n, aabb, min_near,
+                       inds ? inds + base : nullptr, rays_o + 3 * base, rays_d + 3 * base, bg ? bg + 3 * base : nullptr, nears + base, fars + base);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const unsigned long long done = atomicAdd(reinterpret_cast<unsigned long long *>(state + 2), 1ull);
+        if (done == (unsigned long long)gridDim.x * G - 1ull) {  // every workgroup has read the state
+            state[0] = (pose0 + (long long)G) % (long long)P;
+            state[1] = batch0 + (long long)G;
             state[2] = 0;
         }
     }
@@ -473,7 +506,7 @@ __device__ __forceinline__ bool coarse_confine(const Dda &r, const uint8_t *__re
     return true;
 }
 
-__global__ void __launch_bounds__(kBlock) k_march_count_wave(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+__device__ __forceinline__ void march_count_wave_body(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                              const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps,
                                                              uint32_t N, uint32_t C, uint32_t H, const float *__restrict__ nears,
                                                              const float *__restrict__ fars, int32_t *__restrict__ rays, uint32_t perturb,
@@ -521,6 +554,30 @@ __global__ void __launch_bounds__(kBlock) k_march_count_wave(const float *__rest
 #endif
 }
 
+// (the body above is shared by the single launch and the group launch: only the pointers differ)
+__global__ void __launch_bounds__(kBlock) k_march_count_wave(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                                             const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps,
+                                                             uint32_t N, uint32_t C, uint32_t H, const float *__restrict__ nears,
+                                                             const float *__restrict__ fars, int32_t *__restrict__ rays, uint32_t perturb,
+                                                             MarchRayRecords *__restrict__ records, const int32_t *__restrict__ counter,
+                                                             uint32_t fresh, const uint8_t *__restrict__ coarse_mask) {
+    march_count_wave_body(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, rays, perturb, records, counter, fresh,
+                          coarse_mask);
+}
+
+// Group launch (pvd_march_rays_train_group): blockIdx.y = segment j of [G][N ...] inputs, its own records [N + 1] and counter [2]
+__global__ void __launch_bounds__(kBlock) k_march_count_wave_group(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                                                   const uint8_t *__restrict__ grid, float bound, float dt_gamma,
+                                                                   uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H,
+                                                                   const float *__restrict__ nears, const float *__restrict__ fars,
+                                                                   int32_t *__restrict__ rays, uint32_t perturb,
+                                                                   MarchRayRecords *__restrict__ records, const int32_t *__restrict__ counter,
+                                                                   uint32_t fresh, const uint8_t *__restrict__ coarse_mask) {
+    const size_t base = (size_t)blockIdx.y * N;
+    march_count_wave_body(rays_o + 3 * base, rays_d + 3 * base, grid, bound, dt_gamma, max_steps, N, C, H, nears + base, fars + base,
+                          rays + 3 * base, perturb, records + base + blockIdx.y, counter + 2 * (size_t)blockIdx.y, fresh, coarse_mask);
+}
+
 __global__ void __launch_bounds__(kBlock) k_march_write_wave(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                              const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps,
                                                              uint32_t N, uint32_t C, uint32_t H, uint32_t M,
@@ -563,7 +620,7 @@ __global__ void __launch_bounds__(kBlock) k_march_write_wave(const float *__rest
 
 // Write pass from the chunk records, with the exclusive scan of the counts folded in (N small: every workgroup sums the
 // counts of the rays before its own -- a few KB from L2 -- instead of a separate single-workgroup scan launch).
-__global__ void __launch_bounds__(kBlock) k_march_write_records(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+__device__ __forceinline__ void march_write_records_body(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                                const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps,
                                                                uint32_t N, uint32_t C, uint32_t H, uint32_t M,
                                                                const float *__restrict__ nears, const float *__restrict__ fars,
@@ -672,6 +729,34 @@ __global__ void __launch_bounds__(kBlock) k_march_write_records(const float *__r
         emitted += (uint32_t)__popcll(emit_mask);
         last_t = readlane_f(t_after, 63u - (uint32_t)__clzll((long long)emit_mask));
     }
+}
+
+__global__ void __launch_bounds__(kBlock) k_march_write_records(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                                               const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps,
+                                                               uint32_t N, uint32_t C, uint32_t H, uint32_t M,
+                                                               const float *__restrict__ nears, const float *__restrict__ fars,
+                                                               float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas,
+                                                               int32_t *__restrict__ rays, uint32_t perturb,
+                                                               const MarchRayRecords *__restrict__ records, int32_t *__restrict__ counter,
+                                                               uint32_t fresh, const int32_t *__restrict__ budget) {
+    march_write_records_body(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays, perturb,
+                             records, counter, fresh, budget);
+}
+
+// Group launch: blockIdx.y = segment j; its samples go to slice j of [G][M ...] with offsets relative to the slice, its scan starts
+// at its own first ray, its tail is its own slice's, its budget is budget[j * budget_stride] (NULL: M)
+__global__ void __launch_bounds__(kBlock) k_march_write_records_group(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                                                     const uint8_t *__restrict__ grid, float bound, float dt_gamma,
+                                                                     uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
+                                                                     const float *__restrict__ nears, const float *__restrict__ fars,
+                                                                     float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas,
+                                                                     int32_t *__restrict__ rays, uint32_t perturb,
+                                                                     const MarchRayRecords *__restrict__ records, int32_t *__restrict__ counter,
+                                                                     uint32_t fresh, const int32_t *__restrict__ budget, uint32_t budget_stride) {
+    const size_t base = (size_t)blockIdx.y * N, sbase = (size_t)blockIdx.y * M;
+    march_write_records_body(rays_o + 3 * base, rays_d + 3 * base, grid, bound, dt_gamma, max_steps, N, C, H, M, nears + base, fars + base,
+                             xyzs + 3 * sbase, dirs + 3 * sbase, deltas + 2 * sbase, rays + 3 * base, perturb, records + base + blockIdx.y,
+                             counter + 2 * (size_t)blockIdx.y, fresh, budget ? budget + (size_t)blockIdx.y * budget_stride : nullptr);
 }
 
 
@@ -812,12 +897,12 @@ __device__ __forceinline__ void objective_row_grads(const CompositeObjective &ob
 }
 
 // reference: kernel_composite_rays_train_forward, raymarching.cu:504-582
-template <bool EPI, bool OBJ = false>
-__global__ void __launch_bounds__(kBlock) k_composite_fwd_wave(const float *__restrict__ sigmas, const float *__restrict__ rgbs,
-                                                               const float *__restrict__ deltas, const int32_t *__restrict__ rays,
-                                                               uint32_t M, uint32_t N, float *__restrict__ weights_sum,
-                                                               float *__restrict__ depth, float *__restrict__ image, CompositeEpilogue ep,
-                                                               CompositeObjective ob = CompositeObjective{}) {
+template <bool EPI, bool OBJ>
+__device__ __forceinline__ void composite_fwd_wave_body(const float *__restrict__ sigmas, const float *__restrict__ rgbs,
+                                                        const float *__restrict__ deltas, const int32_t *__restrict__ rays,
+                                                        uint32_t M, uint32_t N, float *__restrict__ weights_sum,
+                                                        float *__restrict__ depth, float *__restrict__ image, const CompositeEpilogue &ep,
+                                                        const CompositeObjective &ob) {
     __shared__ float obj_sh[kBlock / kWave];
     if (OBJ && blockIdx.x >= ob.ray_blocks) {
         if (ob.rates_decay && blockIdx.x == ob.ray_blocks && threadIdx.x == 0) ob.rates_decay[1] *= ob.fea_decay;
@@ -880,6 +965,31 @@ __global__ void __launch_bounds__(kBlock) k_composite_fwd_wave(const float *__re
         const float s_img = objective_block_sum(d2, obj_sh);
         if (threadIdx.x == 0) reinterpret_cast<float4 *>(ob.partials)[blockIdx.x] = make_float4(s_img, 0.f, 0.f, 0.f);
     }
+}
+
+template <bool EPI, bool OBJ = false>
+__global__ void __launch_bounds__(kBlock) k_composite_fwd_wave(const float *__restrict__ sigmas, const float *__restrict__ rgbs,
+                                                               const float *__restrict__ deltas, const int32_t *__restrict__ rays,
+                                                               uint32_t M, uint32_t N, float *__restrict__ weights_sum,
+                                                               float *__restrict__ depth, float *__restrict__ image, CompositeEpilogue ep,
+                                                               CompositeObjective ob = CompositeObjective{}) {
+    composite_fwd_wave_body<EPI, OBJ>(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image, ep, ob);
+}
+
+// Group launch of the epilogue form without an objective (pvd_composite_rays_train_bg_forward_group: the frozen teacher's images of G
+// steps): blockIdx.y = segment j, slice j of [G][M ...] samples and [G][N ...] rays, offsets in `rays` relative to the slice
+__global__ void __launch_bounds__(kBlock) k_composite_fwd_wave_group(const float *__restrict__ sigmas, const float *__restrict__ rgbs,
+                                                                     const float *__restrict__ deltas, const int32_t *__restrict__ rays,
+                                                                     uint32_t M, uint32_t N, float *__restrict__ weights_sum,
+                                                                     float *__restrict__ depth, float *__restrict__ image, CompositeEpilogue ep,
+                                                                     uint32_t budget_stride) {
+    const size_t base = (size_t)blockIdx.y * N, sbase = (size_t)blockIdx.y * M;
+    if (ep.bg) ep.bg += 3 * base;
+    ep.nears += base;
+    ep.fars += base;
+    if (ep.budget) ep.budget += (size_t)blockIdx.y * budget_stride;
+    composite_fwd_wave_body<true, false>(sigmas + sbase, rgbs + 3 * sbase, deltas + 2 * sbase, rays + 3 * base, M, N, weights_sum + base,
+                                         depth + base, image + 3 * base, ep, CompositeObjective{});
 }
 
 // reference: kernel_composite_rays_train_backward, raymarching.cu:606-686.  With EPI the incoming gradient is
@@ -1339,6 +1449,65 @@ int pvd_march_rays_train_mask(const float *rays_o, const float *rays_d, const ui
     hipLaunchKernelGGL(k_march_scan, dim3(1), dim3(kScanBlock), 0, s, rays, N, counter);
     hipLaunchKernelGGL(k_march_write_wave, g, b, 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs,
                        deltas, rays, perturb, budget_dev);
+    return check_launch();
+}
+
+// ---- the prefix of a GROUP of G steps, one launch per stage (include/pvd_hip_prefix.h)
+constexpr uint32_t kMaxGroup = 65535;  // segments are gridDim.y
+
+int pvd_make_ray_batch_group(const float *poses, uint32_t P, int64_t *state, uint64_t seed, float fx, float fy, float cx, float cy, uint32_t H,
+                             uint32_t W, uint32_t N, uint32_t G, const float *aabb, float min_near, int64_t *inds, float *rays_o, float *rays_d,
+                             float *bg, float *nears, float *fars, pvd_stream_t stream) {
+    if (N == 0 || G == 0) return PVD_OK;
+    PVD_REQUIRE(poses && P > 0 && state && aabb && rays_o && rays_d && nears && fars && H > 0 && W > 0 && G <= kMaxGroup);
+    PVD_REQUIRE((uint64_t)H * W < (1ull << 32));
+    hipLaunchKernelGGL(k_make_ray_batch_group, dim3(div_up(N, kBlock), G), dim3(kBlock), 0, (hipStream_t)stream, poses, P, (long long *)state,
+                       seed, fx, fy, cx, cy, H, W, N, aabb, min_near, inds, rays_o, rays_d, bg, nears, fars);
+    return check_launch();
+}
+
+size_t pvd_march_group_workspace_bytes(uint32_t N, uint32_t G) { return (size_t)G * pvd_march_workspace_bytes(N); }
+
+int pvd_march_rays_train_group(const float *rays_o, const float *rays_d, const uint8_t *grid, float bound, float dt_gamma, uint32_t max_steps,
+                               uint32_t N, uint32_t G, uint32_t C, uint32_t H, uint32_t M, const float *nears, const float *fars, float *xyzs,
+                               float *dirs, float *deltas, int32_t *rays, int32_t *counter, uint32_t perturb, void *workspace,
+                               size_t workspace_bytes, uint32_t flags, const int32_t *budget_dev, uint32_t budget_stride,
+                               const uint8_t *coarse_mask, pvd_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const bool fresh = (flags & PVD_MARCH_FRESH) != 0;
+    if (G == 0) return PVD_OK;
+    PVD_REQUIRE(G <= kMaxGroup);
+    if (N == 0) {
+        if (fresh && M && xyzs && dirs && deltas && counter) {
+            (void)hipMemsetAsync(xyzs, 0, 3 * (size_t)G * M * sizeof(float), s); (void)hipMemsetAsync(dirs, 0, 3 * (size_t)G * M * sizeof(float), s);
+            (void)hipMemsetAsync(deltas, 0, 2 * (size_t)G * M * sizeof(float), s); (void)hipMemsetAsync(counter, 0, 2 * (size_t)G * sizeof(int32_t), s);
+        }
+        return PVD_OK;
+    }
+    PVD_REQUIRE(rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && rays && counter);
+    PVD_REQUIRE(C >= 1 && C <= 16 && H >= 1 && H <= 1024 && max_steps >= 1);
+    // the records path only: a segment's workgroups sum the counts of the segment's rays before their own (N bounded as in the single
+    // call), and the grid grows with G along y -- G * N may be any size
+    PVD_REQUIRE(workspace && workspace_bytes >= pvd_march_group_workspace_bytes(N, G) && N <= kMarchFusedScanMaxRays);
+    MarchRayRecords *records = (MarchRayRecords *)workspace;
+    const dim3 g(div_up(N, kRaysPerBlock), G), b(kBlock);
+    if ((H & (H - 1u)) || H < PVD_COARSE_BLOCK) coarse_mask = nullptr;
+    hipLaunchKernelGGL(k_march_count_wave_group, g, b, 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, rays,
+                       perturb, records, counter, fresh ? 1u : 0u, coarse_mask);
+    hipLaunchKernelGGL(k_march_write_records_group, g, b, 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs,
+                       dirs, deltas, rays, perturb, records, counter, fresh ? 1u : 0u, budget_dev, budget_stride);
+    return check_launch();
+}
+
+int pvd_composite_rays_train_bg_forward_group(const float *sigmas, const float *rgbs, const float *deltas, const int32_t *rays, uint32_t M,
+                                              uint32_t N, uint32_t G, const float *bg, float bg_scalar, const float *nears, const float *fars,
+                                              float depth_eps, float *weights_sum, float *depth, float *image, const int32_t *budget_dev,
+                                              uint32_t budget_stride, pvd_stream_t stream) {
+    if (N == 0 || G == 0) return PVD_OK;
+    PVD_REQUIRE(sigmas && rgbs && deltas && rays && nears && fars && weights_sum && depth && image && G <= kMaxGroup);
+    const CompositeEpilogue ep{bg, bg_scalar, nears, fars, depth_eps, 0u, budget_dev};
+    hipLaunchKernelGGL(k_composite_fwd_wave_group, dim3(div_up(N, kBlock / kWave), G), dim3(kBlock), 0, (hipStream_t)stream, sigmas, rgbs,
+                       deltas, rays, M, N, weights_sum, depth, image, ep, budget_stride);
     return check_launch();
 }
 

@@ -60,8 +60,18 @@ def hip_ops():
         pvd_hip.make_ray_batch(poses, state, seed, fx, fy, cx, cy, H, W, N, aabb, min_near, None, rays_o, rays_d, bg, nears, fars)
         return rays_o, rays_d, bg, (nears, fars)
 
+    def make_batch_group(poses, state, seed, intrinsics, H, W, N, G, aabb, min_near):
+        """G consecutive batches of make_batch in one launch (pvd_make_ray_batch_group): the same rays, backgrounds and near/far the
+        next G calls of make_batch would return, as slices of (rays_o [G,N,3], rays_d [G,N,3], bg [G,N,3], (nears [G,N], fars [G,N]))."""
+        dev = poses.device
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        rays_o, rays_d, bg, nears, fars = f(G, N, 3), f(G, N, 3), f(G, N, 3), f(G, N), f(G, N)
+        fx, fy, cx, cy = intrinsics
+        pvd_hip.make_ray_batch_group(poses, state, seed, fx, fy, cx, cy, H, W, N, G, aabb, min_near, None, rays_o, rays_d, bg, nears, fars)
+        return rays_o, rays_d, bg, (nears, fars)
+
     def freq_encode(x, bands, include_input=True, out_dtype=torch.float32, row_stride=None):
         return pvd_hip.freq_encode(x, bands, include_input, out_dtype, row_stride)
 
-    return types.SimpleNamespace(freq_encode=freq_encode, make_batch=make_batch, occupancy=pvd_hip.occupancy_backend, raymarching=raymarching, GridEncoder=gridencoder.GridEncoder, SHEncoder=shencoder.SHEncoder,
+    return types.SimpleNamespace(freq_encode=freq_encode, make_batch=make_batch, make_batch_group=make_batch_group, occupancy=pvd_hip.occupancy_backend, raymarching=raymarching, GridEncoder=gridencoder.GridEncoder, SHEncoder=shencoder.SHEncoder,
                                  vm_encode=vmencoder.vm_encode, vm_encode_infer=vmencoder.vm_encode_infer, plenoxel=plenoxel, get_rays=get_rays_fused, fused_head=fusedhead, distill_loss=_distill_loss(), mse_loss=_mse_loss(), flat_adamw=_flat_adamw(), device_type="cuda", name="hip")

@@ -401,6 +401,38 @@ class NeRFRenderer(nn.Module):
         xyzs, dirs, deltas, rays = self._march_train(rays_o, rays_d, nears, fars, counter, perturb, force_all_rays, dt_gamma, max_steps, budget)
         return [xyzs, dirs, deltas, rays], (nears, fars)
 
+    def march_group(self, rays_o, rays_d, nears_fars, dt_gamma=0, perturb=False, max_steps=1024):
+        """march() for G batches in two launches (pvd_march_rays_train_group): rays_o, rays_d [G,N,3], nears / fars [G,N].  Returns
+        (xyzs [G*M,3], dirs [G*M,3], deltas [G*M,2], rays [G,N,3], M): slice j holds, bit for bit, what march() returns for batch j
+        (row count M, budget and coarse mask as _march_train passes them; offsets in rays[j] are relative to slice j)."""
+        import pvd_hip
+        G, N = rays_o.shape[0], rays_o.shape[1]
+        assert self.mean_count > 0 and rays_o.is_cuda, "a group is marched into fixed rows: needs a measured mean_count"
+        nears, fars = nears_fars
+        budget = self._budget()
+        M = self.mean_count + (128 - self.mean_count % 128)  # (raymarching.py:234-238, align 128)
+        budget_dev = None
+        if budget is not None:
+            M, budget_dev = int(budget[0]), budget[1]
+        dev = rays_o.device
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        xyzs, dirs, deltas = f(G * M, 3), f(G * M, 3), f(G * M, 2)
+        rays = torch.empty(G, N, 3, dtype=torch.int32, device=dev)
+        counter = torch.empty(G, 2, dtype=torch.int32, device=dev)  # arrives as scratch, as the single march's (renderer.py:374)
+        pvd_hip.march_rays_train_group(rays_o.float().contiguous(), rays_d.float().contiguous(), self.density_bitfield, self.bound, dt_gamma,
+                                       max_steps, N, G, self.cascade, self.grid_size, M, nears.contiguous(), fars.contiguous(), xyzs, dirs,
+                                       deltas, rays, counter, perturb, fresh=True, budget_dev=budget_dev, coarse_mask=self.coarse_mask())
+        # the ring of 16 step counters (what update_extra_state averages into mean_count, and what a benchmark reports as samples per
+        # step) ends up as G single marches leave it: segment j's counter in slot (local_step + j) % 16, the last 16 segments winning
+        j = max(G - 16, 0)
+        while j < G:
+            slot = (self.local_step + j) % 16
+            run = min(G - j, 16 - slot)
+            self.step_counter[slot:slot + run].copy_(counter[j:j + run])
+            j += run
+        self.local_step += G
+        return xyzs, dirs, deltas, rays, M
+
     def _march_train(self, rays_o, rays_d, nears, fars, counter, perturb, force_all_rays, dt_gamma, max_steps, budget):
         """march_rays_train on this model's occupancy grid, the way run_cuda calls it (align 128, the counter as scratch), with the
         fixed allocation / device-side budget and the coarse mask where the model has them.  (An autograd Function takes positional

@@ -313,14 +313,15 @@ class _TrainerBase:
     # ---- hipGraph capture of the step (launch-bound otherwise: ~330 kernels of a few us each)
     steps_per_replay = 1
 
-    def capture(self, body, warmup=3, steps_per_graph=1):
+    def capture(self, body, warmup=3, steps_per_graph=1, record_body=None):
         """Capture `body()` (forward + loss + backward) and the optimizer into HIP graph(s).  steps_per_graph > 1 records
         that many consecutive steps into the one graph (a replay then costs one graph launch -- ~8 us of launch latency
         between replays in the step's timeline -- for several steps; `replay()` advances the step count accordingly).  Single GPU: one graph for
         the whole step.  Ray-DP: the capture is SEGMENTED at every collective (`SegmentedCapture`): the all-reduce of the
         four loss sums and the gradient exchange run eagerly between graph replays, so nothing depends on the
         communication library being capturable.  Everything that changes per step lives on the device (lr, loss rates,
-        pose index, RNG state, loss scale), so a replay is a faithful step."""
+        pose index, RNG state, loss scale), so a replay is a faithful step.  record_body: what is recorded instead of `body`
+        (the warm-up steps still run `body`): the grouped recording of DistillTrainer."""
         assert self.device_type == "cuda"
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -347,7 +348,7 @@ class _TrainerBase:
             with cap:
                 for k_rec in range(max(1, int(steps_per_graph))):
                     self._zero_grads(first_in_recording=k_rec == 0)
-                    self._static_out = body()
+                    self._static_out = (record_body or body)()
                     if os.environ.get("PVD_TEST_FAIL_IN_CAPTURE") == "1":  # exercises the callers' eager fallback
                         raise RuntimeError("forced failure inside the capture (PVD_TEST_FAIL_IN_CAPTURE)")
                     self._backward(self._static_out[0])
@@ -469,6 +470,54 @@ class DistillTrainer(_TrainerBase):
         tea = self.model_tea
         attrs = {k: getattr(tea, k, None) for k in ("feature_sigma_color", "sigma_l", "color_l")}
         return dict(part, out_tea=out_tea, tea_attrs={k: v for k, v in attrs.items() if torch.is_tensor(v)})
+
+    def prefetch_group(self, batch_group_fn, G):
+        """prefetch() for G consecutive steps with ONE launch per stage (include/pvd_hip_prefix.h): G batches, the march of their
+        G x N rays as G segments, the frozen teacher's forward over the G x M rows of the group (the same kernel on a G times longer
+        launch: it pulls the hash table through the L2s once per group instead of once per step) and its compositing.  Returns a list
+        of G prefixes, views of slice j of the group's buffers, each bit for bit what prefetch() returns for that step."""
+        stu, tea = self.model_stu, self.model_tea
+        rm = stu.rm
+        rays_o, rays_d, bg, nf = batch_group_fn(G)
+        N = rays_o.shape[1]
+        amp = self.fp16 and self.device_type == "cuda"
+        kw = self.render_kwargs()
+        xyzs, dirs, deltas, rays, M = stu.march_group(rays_o, rays_d, nf, dt_gamma=kw["dt_gamma"], perturb=True, max_steps=kw["max_steps"])
+        with torch.autocast(self.device_type, dtype=torch.float16, enabled=amp), torch.no_grad():
+            sigmas, rgbs = tea(xyzs, dirs)
+            attrs = {k: getattr(tea, k, None) for k in ("feature_sigma_color", "sigma_l", "color_l")}
+            if tea.density_scale != 1:
+                sigmas = tea.density_scale * sigmas
+        import pvd_hip
+        sigmas, rgbs = sigmas.float().contiguous(), rgbs.float().contiguous()
+        ws = torch.empty(G, N, dtype=torch.float32, device=sigmas.device)
+        depth, image = torch.empty_like(ws), torch.empty(G, N, 3, dtype=torch.float32, device=sigmas.device)
+        # (the teacher composites inherited samples: rows M, no device-side budget, eps 1e-6 -- run_cuda's training branch)
+        pvd_hip.composite_rays_train_bg_forward_group(sigmas, rgbs, deltas, rays, M, N, G, bg.contiguous(), 0.0, nf[0], nf[1], 1e-6, ws, depth, image)
+        pres = []
+        for j in range(G):
+            sl = slice(j * M, (j + 1) * M)
+            out_tea = {"depth": depth[j].view(1, N), "image": image[j].view(1, N, 3), "inherited_params": None, "sigmas": sigmas[sl], "rays": rays[j],
+                       "nears_fars": (nf[0][j], nf[1][j])}
+            pres.append(dict(rays_o=rays_o[j:j + 1], rays_d=rays_d[j:j + 1], bg=bg[j:j + 1], inh=[xyzs[sl], dirs[sl], deltas[sl], rays[j]],
+                             nf=(nf[0][j], nf[1][j]), out_tea=out_tea, tea_attrs={k: v[sl] for k, v in attrs.items() if torch.is_tensor(v)}))
+        return pres
+
+    def _prefix_group(self, steps_per_graph, batch_group_fn):
+        """G of the grouped recording (PVD_PREFIX_GROUP, default 20: the largest measured, profiles/batched_prefix.txt; 1 = per step): the
+        largest divisor of the steps per graph that does not exceed it, and only where the group's
+        launches exist for the two models (a frozen teacher without a background model, the student's march into fixed rows)."""
+        try:
+            G = int(os.environ.get("PVD_PREFIX_GROUP", "20") or 20)
+        except ValueError:
+            G = 1
+        tea, stu = self.model_tea, self.model_stu
+        if (G <= 1 or batch_group_fn is None or self.device_type != "cuda" or tea.bg_radius > 0 or stu.bg_radius > 0 or not stu.cuda_ray
+                or stu.mean_count <= 0 or getattr(tea, "teacher_variant", False)):
+            return 1
+        while steps_per_graph % G:
+            G -= 1
+        return G
 
     def compute_loss(self, rays_o, rays_d, bg_color, nears_fars=None, pre=None):
         o, stu, tea = self.opt, self.model_stu, self.model_tea
@@ -614,10 +663,11 @@ class DistillTrainer(_TrainerBase):
         self._backward_and_step(loss)
         return loss.detach(), info, pred_stu, pred_tea
 
-    def capture_step(self, batch_fn, steps_per_graph=1):
+    def capture_step(self, batch_fn, steps_per_graph=1, batch_group_fn=None):
         """Capture `batch_fn() -> (rays_o, rays_d, bg)` + the whole step into HIP graph(s); the stage
         (which loss terms exist) is frozen at capture time, so re-capture when the stage changes.  Three eager warm-up
-        steps run first (real steps: global_step advances by 3)."""
+        steps run first (real steps: global_step advances by 3).  batch_group_fn(G): the next G batches of batch_fn as slices, for
+        the grouped recording (prefetch_group)."""
         def body():
             rays_o, rays_d, bg, *rest = batch_fn()
             with torch.autocast(self.device_type, dtype=torch.float16, enabled=self.fp16):
@@ -631,6 +681,7 @@ class DistillTrainer(_TrainerBase):
             self.sync_sharded_state()  # (a sharded recording leaves the other ranks' rows' moments behind: current before anything else runs)
         self._replay_owes_part_a = None  # what replay() tells the optimizer afterwards belongs to the recording made below
         self.fused_spans = None
+        self.prefix_group = 1
         stage = self._stage_of(self.global_step)
         assert self._stage_of(self.global_step + warm) == stage, \
             "capture_step: the %d warm-up steps cross a stage boundary (global_step %d); step eagerly past it first" % (warm, self.global_step)
@@ -667,6 +718,21 @@ class DistillTrainer(_TrainerBase):
                 self.pipelined_ingraph = False
                 self.capture_fallback = "back-to-back"
                 out = self.capture(body, warmup=0, steps_per_graph=steps_per_graph)  # the same steps recorded back to back (warm-ups done)
+        elif not self.dp.enabled and stage == 3 and stu_marches and self._prefix_group(steps_per_graph, batch_group_fn) > 1:
+            # single GPU, steps back to back (no second chain): the prefix of a GROUP of G steps in front of the group's first step, one
+            # launch per stage; step j of the group reads slice j.  Same batches in the same order as the per-step recording.
+            G = self._prefix_group(steps_per_graph, batch_group_fn)
+            group = {"k": 0, "pres": None}
+
+            def body_grouped():
+                if group["k"] % G == 0:
+                    group["pres"] = self.prefetch_group(batch_group_fn, G)
+                pre = group["pres"][group["k"] % G]
+                group["k"] += 1
+                with torch.autocast(self.device_type, dtype=torch.float16, enabled=self.fp16):
+                    return self.compute_loss(None, None, None, pre=pre)
+            out = self.capture(body, steps_per_graph=steps_per_graph, record_body=body_grouped)
+            self.prefix_group = G
         else:
             out = self.capture(body, steps_per_graph=steps_per_graph)
         self._captured_stage = self._stage_of(self.global_step)

@@ -139,18 +139,21 @@ class DistillWorkload:
         bg = torch.rand(1, opt.num_rays, 3, device=self.device, generator=self.gen)
         return r["rays_o"], r["rays_d"], bg
 
+    def _init_batch_state(self):
+        if not hasattr(self, "_batch_state"):
+            self._batch_state = torch.zeros(3, dtype=torch.int64, device=self.device)
+            self._poses_c = self.poses.float().contiguous()
+            # every ray-DP rank must draw its own pixels: the rank is part of the key (the CUDA seed alone is the same
+            # on every rank unless the caller seeds per rank)
+            self._batch_seed = 0x5eed + 1000003 * int(torch.cuda.initial_seed() % (2 ** 31)) + 0x9E3779B1 * self.dp_rank
+
     def device_batch(self):
         """next_batch() with nothing on the host: pose index and RNG state live on the device, so the batch
         generation can sit inside a captured HIP graph (default CUDA generator, graph-safe)."""
         opt = self.opt
         mk = getattr(self.ops, "make_batch", None)
         if mk is not None:  # pose selection, pixel ids, rays, background and near/far in one kernel
-            if not hasattr(self, "_batch_state"):
-                self._batch_state = torch.zeros(3, dtype=torch.int64, device=self.device)
-                self._poses_c = self.poses.float().contiguous()
-                # every ray-DP rank must draw its own pixels: the rank is part of the key (the CUDA seed alone is the same
-                # on every rank unless the caller seeds per rank)
-                self._batch_seed = 0x5eed + 1000003 * int(torch.cuda.initial_seed() % (2 ** 31)) + 0x9E3779B1 * self.dp_rank
+            self._init_batch_state()
             return mk(self._poses_c, self._batch_state, self._batch_seed, BLENDER_INTRINSICS, 800, 800, opt.num_rays,
                       self.stu.aabb_train, self.stu.min_near)
         if not hasattr(self, "_pose_idx"):
@@ -162,11 +165,18 @@ class DistillWorkload:
         bg = torch.rand(1, opt.num_rays, 3, device=self.device)
         return r["rays_o"], r["rays_d"], bg
 
+    def device_batch_group(self, G):
+        """The next G batches of device_batch() in one launch (same pose order, same random streams, the device state advanced by G)."""
+        self._init_batch_state()
+        return self.ops.make_batch_group(self._poses_c, self._batch_state, self._batch_seed, BLENDER_INTRINSICS, 800, 800, self.opt.num_rays, G,
+                                         self.stu.aabb_train, self.stu.min_near)
+
     def enable_graph(self, steps_per_graph=1):
         """Whole-step hipGraph capture (GPU only).  steps_per_graph > 1: every step() call then runs that many training steps
         (one graph launch); `steps_per_call` says how many."""
         assert not self.opt.update_stu_extra, "update_stu_extra rewrites the occupancy grid between steps: run eagerly"
-        self.trainer.capture_step(self.device_batch, steps_per_graph=steps_per_graph)
+        group_fn = self.device_batch_group if getattr(self.ops, "make_batch_group", None) is not None else None
+        self.trainer.capture_step(self.device_batch, steps_per_graph=steps_per_graph, batch_group_fn=group_fn)
         self._graph = True
 
     @property

@@ -111,11 +111,21 @@ ENTRY_POINTS_MESH_SIMPLIFY = ("pvd_mesh_simplify_workspace_bytes", "pvd_mesh_sim
 ENTRY_POINTS_MESH_RAY = ("pvd_mesh_ray_workspace_bytes", "pvd_mesh_ray_count", "pvd_mesh_ray_build", "pvd_mesh_ray_cast")
 # ... and the Taubin smoothing of include/pvd_hip_mesh_smooth.h (tests/test_abi_mesh_smooth.py)
 ENTRY_POINTS_MESH_SMOOTH = ("pvd_mesh_smooth_workspace_bytes", "pvd_mesh_smooth_build", "pvd_mesh_smooth_run")
+# ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
+ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
+                       "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
               + ENTRY_POINTS_MESH_SMOOTH):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
+# (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
+# grouped one fails loudly at its first call)
+HAS_PREFIX_GROUP = all(hasattr(_lib, _name) for _name in ENTRY_POINTS_PREFIX)
+if HAS_PREFIX_GROUP:
+    for _name in ENTRY_POINTS_PREFIX:
+        getattr(_lib, _name).restype = ctypes.c_int
+    _lib.pvd_march_group_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_march_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_dist_workspace_bytes.restype = ctypes.c_size_t
@@ -1066,6 +1076,80 @@ def composite_rays_train_bg_backward(grad_weights_sum, grad_image, sigmas, rgbs,
           _p(weights_sum), _p(image), _u32(M), _u32(N), _p(bg), _f32(bg_scalar), _p(grad_sigmas), _p(grad_rgbs), _u32(1 if fresh else 0),
           _p(budget_dev))
 
+
+
+# --------------------------------------------------------------------------- the prefix of G steps at once (include/pvd_hip_prefix.h)
+def make_ray_batch_group(poses, state, seed, fx, fy, cx, cy, H, W, N, G, aabb, min_near, inds, rays_o, rays_d, bg, nears, fars):
+    """G consecutive batches of make_ray_batch in one launch; outputs [G][N ...]; the state advances by G."""
+    dev = _dev(poses, state, aabb, inds, rays_o, rays_d, bg, nears, fars)
+    _f32_all(poses=poses, aabb=aabb, rays_o=rays_o, rays_d=rays_d, nears=nears, fars=fars)
+    _want(state, torch.int64, "state")
+    if inds is not None:
+        _want(inds, torch.int64, "inds")
+    if bg is not None:
+        _want(bg, torch.float32, "bg")
+    if state.numel() < 3:
+        raise PvdHipError("state must hold 3 int64 values")
+    for name, t, per in (("inds", inds, 1), ("rays_o", rays_o, 3), ("rays_d", rays_d, 3), ("bg", bg, 3), ("nears", nears, 1), ("fars", fars, 1)):
+        if t is not None and t.numel() != G * N * per:
+            raise PvdHipError("%s must hold G * N * %d elements" % (name, per))
+    _call("pvd_make_ray_batch_group", dev, _p(poses), _u32(poses.shape[0]), _p(state), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _f32(fx),
+          _f32(fy), _f32(cx), _f32(cy), _u32(H), _u32(W), _u32(N), _u32(G), _p(aabb), _f32(min_near), _p(inds), _p(rays_o), _p(rays_d), _p(bg),
+          _p(nears), _p(fars))
+
+
+def _march_group_workspace(dev, N, G):
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, N, G)
+    ws = _march_ws.get(key)
+    if ws is None:
+        ws = torch.empty(int(_lib.pvd_march_group_workspace_bytes(_u32(N), _u32(G))), dtype=torch.uint8, device=dev)
+        _march_ws[key] = ws
+    return ws
+
+
+def march_rays_train_group(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, G, C, H, M, nears, fars, xyzs, dirs, deltas, rays, counter,
+                           perturb, fresh=False, budget_dev=None, coarse_mask=None):
+    """march_rays_train over G segments of N rays (rays_o [G,N,3] ... rays [G,N,3], counter [G,2], samples [G,M,..]) in two launches;
+    budget_dev: None, one DEVICE int32 for every segment, or int32 [G] (one per segment)."""
+    dev = _dev(rays_o, rays_d, grid, nears, fars, xyzs, dirs, deltas, rays, counter, budget_dev, coarse_mask)
+    if coarse_mask is not None:
+        _want(coarse_mask, torch.uint8, "coarse_mask")
+        if coarse_mask.numel() != coarse_mask_bytes(C, H):
+            raise PvdHipError("coarse_mask must hold C * (H/8)^3 bytes")
+    stride = 0
+    if budget_dev is not None:
+        _want(budget_dev, torch.int32, "budget_dev")
+        if budget_dev.numel() not in (1, G):
+            raise PvdHipError("budget_dev must hold 1 or G values")
+        stride = 1 if (budget_dev.numel() == G and G > 1) else 0
+    _f32_all(rays_o=rays_o, rays_d=rays_d, nears=nears, fars=fars, xyzs=xyzs, dirs=dirs, deltas=deltas)
+    _want(grid, torch.uint8, "grid"), _want(rays, torch.int32, "rays"), _want(counter, torch.int32, "counter")
+    if (rays_o.numel() != 3 * G * N or rays_d.numel() != 3 * G * N or nears.numel() != G * N or fars.numel() != G * N or rays.numel() != 3 * G * N
+            or counter.numel() != 2 * G or xyzs.numel() != 3 * G * M or dirs.numel() != 3 * G * M or deltas.numel() != 2 * G * M):
+        raise PvdHipError("group buffers must be [G][N ...] / [G][M ...]")
+    if N > 16384:
+        raise PvdHipError("a segment holds at most 16384 rays")
+    ws = _march_group_workspace(dev, N, G)
+    _call("pvd_march_rays_train_group", dev, _p(rays_o), _p(rays_d), _p(grid), _f32(bound), _f32(dt_gamma), _u32(max_steps), _u32(N), _u32(G),
+          _u32(C), _u32(H), _u32(M), _p(nears), _p(fars), _p(xyzs), _p(dirs), _p(deltas), _p(rays), _p(counter), _u32(int(perturb)), _p(ws),
+          ctypes.c_size_t(ws.numel()), _u32(1 if fresh else 0), _p(budget_dev), _u32(stride), _p(coarse_mask))
+
+
+def composite_rays_train_bg_forward_group(sigmas, rgbs, deltas, rays, M, N, G, bg, bg_scalar, nears, fars, depth_eps, weights_sum, depth, image,
+                                          budget_dev=None):
+    dev = _dev(sigmas, rgbs, deltas, rays, bg, nears, fars, weights_sum, depth, image, budget_dev)
+    _f32_all(sigmas=sigmas, rgbs=rgbs, deltas=deltas, nears=nears, fars=fars, weights_sum=weights_sum, depth=depth, image=image)
+    _want(rays, torch.int32, "rays")
+    if (sigmas.numel() != G * M or rgbs.numel() != 3 * G * M or deltas.numel() != 2 * G * M or rays.numel() != 3 * G * N or nears.numel() != G * N
+            or fars.numel() != G * N or weights_sum.numel() != G * N or depth.numel() != G * N or image.numel() != 3 * G * N
+            or (bg is not None and bg.numel() != 3 * G * N)):
+        raise PvdHipError("group buffers must be [G][N ...] / [G][M ...]")
+    stride = 0
+    if budget_dev is not None:
+        _want(budget_dev, torch.int32, "budget_dev")
+        stride = 1 if (budget_dev.numel() == G and G > 1) else 0
+    _call("pvd_composite_rays_train_bg_forward_group", dev, _p(sigmas), _p(rgbs), _p(deltas), _p(rays), _u32(M), _u32(N), _u32(G), _p(bg),
+          _f32(bg_scalar), _p(nears), _p(fars), _f32(depth_eps), _p(weights_sum), _p(depth), _p(image), _p(budget_dev), _u32(stride))
 
 
 def composite_objective_blocks(N, rows, fixed=False):
