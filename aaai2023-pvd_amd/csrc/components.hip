@@ -16,7 +16,7 @@
 // A kernel boundary is the only thing that makes one phase's plain stores visible to the next phase.  Inside k_cc_merge a parent is
 // only ever taken from an agent-scope relaxed atomic load or from the value an atomicMin returned.  No loop waits for a store of
 // another lane or workgroup: every loop below states why each trip lowers an index or leaves.
-#include "pvd_device.h"
+#include "block_scan.h"
 
 #include "../../include/pvd_hip_components.h"
 
@@ -24,8 +24,6 @@ namespace {
 
 using namespace pvd;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
 constexpr int kFlatThreads = 1024;
 constexpr int kFlatWaves = kFlatThreads / kWave;
 
@@ -178,19 +176,8 @@ __global__ __launch_bounds__(kThreads) void k_cc_largest(const uint32_t *__restr
     __shared__ unsigned long long red[kWaves];
     const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
     const uint32_t s = n < N ? sizes[n] : 0u;
-    unsigned long long v = s ? ((unsigned long long)s << 32) | (unsigned long long)(~n) : 0ull;
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_down(v, o, kWave);
-        v = w > v ? w : v;
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) v = red[w] > v ? red[w] : v;
-        if (v) atomicMax(best, v);
-    }
+    const unsigned long long v = block_max(s ? ((unsigned long long)s << 32) | (unsigned long long)(~n) : 0ull, red);
+    if (threadIdx.x == 0 && v) atomicMax(best, v);
 }
 
 __global__ void k_cc_unpack(uint32_t *stats) {
@@ -204,8 +191,8 @@ __global__ __launch_bounds__(kThreads) void k_cc_filter(const float *field, cons
                                                        const uint32_t *__restrict__ sizes, const uint32_t *__restrict__ stats, uint32_t N,
                                                        float thresh, uint32_t min_points, uint32_t largest_only, float *out,
                                                        uint32_t *__restrict__ kept) {
-    __shared__ uint32_t red[2][kWaves];
-    const uint32_t n = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & (kWave - 1);
+    __shared__ uint32_t red[kWaves];
+    const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
     bool keep = false, is_root = false;
     if (n < N) {
         const float v = field[n];
@@ -217,18 +204,10 @@ __global__ __launch_bounds__(kThreads) void k_cc_filter(const float *field, cons
         out[n] = (lab >= 0 && !keep) ? thresh : v;
     }
     const uint64_t kc = __ballot(keep && is_root), kp = __ballot(keep);
-    if (lane == 0) {
-        red[0][threadIdx.x / kWave] = (uint32_t)__popcll(kc);
-        red[1][threadIdx.x / kWave] = (uint32_t)__popcll(kp);
-    }
-    __syncthreads();
+    // both counts in one word: a workgroup keeps at most kThreads = 256 components (low half) and 256 points (high half)
+    const uint32_t s = block_sum_of_waves((uint32_t)__popcll(kc) | ((uint32_t)__popcll(kp) << 16), red);
     if (threadIdx.x == 0) {
-        uint32_t a = 0, b = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            a += red[0][w];
-            b += red[1][w];
-        }
+        const uint32_t a = s & 0xffffu, b = s >> 16;
         if (a) atomicAdd(kept + 0, a);
         if (b) atomicAdd(kept + 1, b);
     }

@@ -6,17 +6,18 @@
 // k_mesh_count    one lane per lattice point (k fastest, so a wave reads consecutive floats): the 8 corners of the point's cell ->
 //                 the 7-bit mask of owned edges that carry a vertex and the number of triangles of the owned cell (0..12), one byte
 //                 each, and the sums of both over the workgroup's 256 points.
-// k_mesh_scan     ONE workgroup walks the per-workgroup sums in chunks of 8192 with a running carry: exclusive scan in place, the
-//                 two totals to totals_dev.
+// k_mesh_scan     ONE workgroup: the exclusive scan of both arrays of sums in place, side by side (scan_sums, csrc/block_scan.h);
+//                 the two totals to totals_dev.
 // k_mesh_offsets  one lane per lattice point: exclusive scan of the two byte counts inside the workgroup + the workgroup's base
 //                 -> the point's first vertex index and first triangle index.
+// Inside a workgroup the two counts travel as one word (kPairShift): 256 points own at most 1792 vertices and 3072 triangles.
 // k_mesh_emit     one lane per lattice point: the owned vertices (world positions) and the owned cell's triangles; a triangle
 //                 finds a vertex another point owns from that point's mask and first vertex index.
 // k_mesh_normals  (include/pvd_hip_mesh_attr.h) one lane per lattice point: the normal of every owned vertex, from the gradient of
 //                 the field at the two ends of its edge; reads the mask and the first vertex index the passes above left.
-// Reduce-then-scan in separate launches: no workgroup waits on another one of the same launch, nothing is atomic, and the
-// output does not depend on the order in which workgroups run.
-#include "pvd_device.h"
+// The count -> one-workgroup scan -> offsets shape of csrc/block_scan.h: no workgroup waits on another one of the same launch,
+// nothing is atomic, and the output does not depend on the order in which workgroups run.
+#include "block_scan.h"
 
 #include "../../include/pvd_hip_mesh.h"
 #include "../../include/pvd_hip_mesh_attr.h"
@@ -24,13 +25,6 @@
 namespace {
 
 using namespace pvd;
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kScanThreads = 1024;
-constexpr int kScanWaves = kScanThreads / kWave;
-constexpr int kScanItems = 8;
-constexpr uint32_t kScanChunk = kScanThreads * kScanItems;
 
 // corner / direction code of an offset (ox, oy, oz) in {0,1}^3: ox * 4 + oy * 2 + oz, so codes order like linear indices
 // edge slot of a direction code: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1) = slots 0..6
@@ -95,26 +89,15 @@ __device__ __forceinline__ uint32_t tet_bits(uint32_t in, uint32_t tet) {
     return (in & 1u) | (((in >> tet_corner(tet, 1)) & 1u) << 1) | (((in >> tet_corner(tet, 2)) & 1u) << 2) | (((in >> 7) & 1u) << 3);
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-    return v;
-}
-// inclusive scan over the wave
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t w = __shfl_up(v, o, kWave);
-        if (lane >= (uint32_t)o) v += w;
-    }
-    return v;
-}
+// Inside a workgroup the vertex count (low half) and the triangle count (high half) of a point are summed and scanned as one word:
+// a byte count is at most 255, so neither half of a sum over kThreads points reaches 2^16, whatever the bytes hold.
+constexpr uint32_t kPairShift = 16, kPairMask = 0xffffu;
+static_assert(255u * kThreads <= kPairMask, "a half of the pair overflows into the other");
 
 __global__ __launch_bounds__(kThreads) void k_mesh_count(const float *__restrict__ u, uint32_t R, uint32_t N, float thresh,
                                                         uint8_t *__restrict__ vmask, uint8_t *__restrict__ tcnt,
                                                         uint32_t *__restrict__ bsum_v, uint32_t *__restrict__ bsum_t) {
-    __shared__ uint32_t red[2][kWaves];
+    __shared__ uint32_t red[kWaves];
     const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
     uint32_t nv = 0, nt = 0;
     if (n < N) {
@@ -133,101 +116,35 @@ __global__ __launch_bounds__(kThreads) void k_mesh_count(const float *__restrict
         vmask[n] = (uint8_t)m;
         tcnt[n] = (uint8_t)nt;
     }
-    const uint32_t sv = wave_sum_u32(nv), st = wave_sum_u32(nt);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        red[0][threadIdx.x / kWave] = sv;
-        red[1][threadIdx.x / kWave] = st;
-    }
-    __syncthreads();
+    const uint32_t s = block_sum(nv | (nt << kPairShift), red);
     if (threadIdx.x == 0) {
-        uint32_t a = 0, b = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            a += red[0][w];
-            b += red[1][w];
-        }
-        bsum_v[blockIdx.x] = a;
-        bsum_t[blockIdx.x] = b;
+        bsum_v[blockIdx.x] = s & kPairMask;
+        bsum_t[blockIdx.x] = s >> kPairShift;
     }
 }
 
 // one workgroup; sums [NB] -> exclusive scan in place, for both arrays; totals[0], totals[1]
 __global__ __launch_bounds__(kScanThreads) void k_mesh_scan(uint32_t *__restrict__ bsum_v, uint32_t *__restrict__ bsum_t, uint32_t NB,
                                                            uint32_t *__restrict__ totals) {
-    __shared__ uint32_t wtot[2][kScanWaves];
-    const uint32_t t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-    uint32_t carry_v = 0, carry_t = 0;
-    for (uint32_t base = 0; base < NB; base += kScanChunk) {  // the trip count is the same for every thread
-        const uint32_t first = base + t * kScanItems;
-        uint32_t a[kScanItems], b[kScanItems], sa = 0, sb = 0;
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            const bool ok = first + q < NB;
-            a[q] = ok ? bsum_v[first + q] : 0u;
-            b[q] = ok ? bsum_t[first + q] : 0u;
-            sa += a[q];
-            sb += b[q];
-        }
-        const uint32_t ia = wave_scan_u32(sa), ib = wave_scan_u32(sb);
-        if (lane == kWave - 1) {
-            wtot[0][wave] = ia;
-            wtot[1][wave] = ib;
-        }
-        __syncthreads();
-        uint32_t before_a = 0, before_b = 0, all_a = 0, all_b = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kScanWaves; ++w) {
-            const uint32_t x = wtot[0][w], y = wtot[1][w];
-            if (w < wave) {
-                before_a += x;
-                before_b += y;
-            }
-            all_a += x;
-            all_b += y;
-        }
-        __syncthreads();  // wtot is rewritten by the next chunk
-        uint32_t ea = carry_v + before_a + (ia - sa), eb = carry_t + before_b + (ib - sb);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            if (first + q < NB) {
-                bsum_v[first + q] = ea;
-                bsum_t[first + q] = eb;
-            }
-            ea += a[q];
-            eb += b[q];
-        }
-        carry_v += all_a;
-        carry_t += all_b;
-    }
-    if (t == 0) {
-        totals[0] = carry_v;
-        totals[1] = carry_t;
+    uint32_t *const sums[2] = {bsum_v, bsum_t};
+    uint32_t total[2];
+    scan_sums(sums, NB, total);
+    if (threadIdx.x == 0) {
+        totals[0] = total[0];
+        totals[1] = total[1];
     }
 }
 
 __global__ __launch_bounds__(kThreads) void k_mesh_offsets(const uint8_t *__restrict__ vmask, const uint8_t *__restrict__ tcnt, uint32_t N,
                                                           const uint32_t *__restrict__ bsum_v, const uint32_t *__restrict__ bsum_t,
                                                           uint32_t *__restrict__ voff, uint32_t *__restrict__ toff) {
-    __shared__ uint32_t wtot[2][kWaves];
-    const uint32_t n = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    __shared__ uint32_t wtot[kWaves];
+    const uint32_t n = blockIdx.x * kThreads + threadIdx.x;
     const uint32_t nv = n < N ? (uint32_t)__popc((uint32_t)vmask[n]) : 0u, nt = n < N ? (uint32_t)tcnt[n] : 0u;
-    const uint32_t iv = wave_scan_u32(nv), it = wave_scan_u32(nt);
-    if (lane == kWave - 1) {
-        wtot[0][wave] = iv;
-        wtot[1][wave] = it;
-    }
-    __syncthreads();
-    uint32_t bv = bsum_v[blockIdx.x], bt = bsum_t[blockIdx.x];
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) {
-        if (w < wave) {
-            bv += wtot[0][w];
-            bt += wtot[1][w];
-        }
-    }
+    const uint32_t e = block_exclusive(nv | (nt << kPairShift), wtot);
     if (n < N) {
-        voff[n] = bv + (iv - nv);
-        toff[n] = bt + (it - nt);
+        voff[n] = bsum_v[blockIdx.x] + (e & kPairMask);
+        toff[n] = bsum_t[blockIdx.x] + (e >> kPairShift);
     }
 }
 

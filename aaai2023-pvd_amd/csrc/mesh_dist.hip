@@ -3,16 +3,14 @@
 //
 // k_md_count     one lane per triangle: validity, the centroid's cell (kept per triangle for the fill pass), one integer atomicAdd
 //                on the cell's count, one atomicMax on rho (the bits of a non-negative float order like unsigned integers).
-// k_md_blocksum  one lane per cell: the sum of the counts of the workgroup's 256 cells.
-// k_md_scan      ONE workgroup walks those sums in chunks of 8192 with a running carry: exclusive scan in place, the total (the
-//                number of valid triangles) to start[C] and to the header.
-// k_md_offsets   one lane per cell: exclusive scan of the counts inside the workgroup + the workgroup's base -> the cell's start,
-//                and the same value as the cell's fill cursor.
+// k_blocksum, k_scan, k_offsets   (csrc/block_scan.h) the per-cell counts -> the cell's start and, the same value,
+//                its fill cursor; the total (the number of valid triangles) to start[C] and to the header.
 // k_md_fill      one lane per triangle: a slot from the cell's cursor (integer atomicAdd), the nine coordinates and the index into it.
 // k_md_query     one lane per point: rings of cells around the point's cell until no unvisited triangle can win.
-// The same count -> one-block scan -> offsets shape as csrc/mesh.hip: no workgroup waits on another one of the same launch, and no
-// loop retries an atomic.  The order of the triangles inside a cell depends on the run; the query's (d, index) minimum does not.
-#include "pvd_device.h"
+// The count -> one-workgroup scan -> offsets shape of csrc/block_scan.h: no workgroup waits on another one of the same launch, and
+// no loop retries an atomic.  The order of the triangles inside a cell depends on the run; the query's (d, index) minimum does not.
+#include "block_scan.h"
+#include "mesh_grid.h"
 
 #include "../../include/pvd_hip_mesh_dist.h"
 
@@ -20,12 +18,6 @@ namespace {
 
 using namespace pvd;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kScanThreads = 1024;
-constexpr int kScanWaves = kScanThreads / kWave;
-constexpr int kScanItems = 8;
-constexpr uint32_t kScanChunk = kScanThreads * kScanItems;
 constexpr uint32_t kNoCell = 0xffffffffu;
 constexpr uint32_t kMaxT = 0x7fffffffu;
 
@@ -48,15 +40,10 @@ inline Layout layout(uint32_t T, uint32_t G) {
     return l;
 }
 
-// the pure parts (cells, distance, ring walk) are __host__ __device__: a CPU build can walk the same code
-#define PVD_HD __host__ __device__ __forceinline__
-
-PVD_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
-PVD_HD uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
+// the pure parts (cells, distance, ring walk) are PVD_HD, __host__ __device__: a CPU build can walk the same code
 PVD_HD float next_up(float x) { return u2f(f2u(x) + 1u); }  // the float above a finite non-negative float
 PVD_HD int imin(int a, int b) { return a < b ? a : b; }
 PVD_HD int imax(int a, int b) { return a > b ? a : b; }
-PVD_HD uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 struct Box {  // per axis: the origin, cells per unit length (0 on a flat axis); h_min over the axes that are not flat (0: none)
     double lo[3], inv_h[3], h_min;
@@ -78,32 +65,6 @@ PVD_HD Box box_of(const float *__restrict__ bmin3, const float *__restrict__ bma
         }
     }
     return b;
-}
-
-// the cell coordinate of x along axis a: one monotone function of x, used for centroids and for points alike
-PVD_HD int cell_axis(const Box &b, int a, double x, uint32_t G) {
-    const double v = (x - b.lo[a]) * b.inv_h[a];
-    return v >= 1.0 ? (int)fmin(v, (double)(G - 1)) : 0;  // NaN and everything below 1 -> 0
-}
-
-PVD_HD bool finite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for NaN
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-    return v;
-}
-// inclusive scan over the wave
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t w = __shfl_up(v, o, kWave);
-        if (lane >= (uint32_t)o) v += w;
-    }
-    return v;
 }
 
 // the cell of a valid triangle's centroid, and the largest distance from the centroid to a corner, rounded up twice over: the
@@ -149,78 +110,6 @@ __global__ __launch_bounds__(kThreads) void k_md_count(const float *__restrict__
         }
     }
     tcell[t] = cell;
-}
-
-__global__ __launch_bounds__(kThreads) void k_md_blocksum(const uint32_t *__restrict__ cursor, uint32_t C, uint32_t *__restrict__ bsum) {
-    __shared__ uint32_t red[kWaves];
-    const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-    const uint32_t s = wave_sum_u32(c < C ? cursor[c] : 0u);
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) a += red[w];
-        bsum[blockIdx.x] = a;
-    }
-}
-
-// one workgroup; sums [NB] -> exclusive scan in place; the total to total_a and total_b
-__global__ __launch_bounds__(kScanThreads) void k_md_scan(uint32_t *__restrict__ bsum, uint32_t NB, uint32_t *__restrict__ total_a,
-                                                         uint32_t *__restrict__ total_b) {
-    __shared__ uint32_t wtot[kScanWaves];
-    const uint32_t t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < NB; base += kScanChunk) {  // the trip count is the same for every thread
-        const uint32_t first = base + t * kScanItems;
-        uint32_t a[kScanItems], sa = 0;
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            a[q] = first + q < NB ? bsum[first + q] : 0u;
-            sa += a[q];
-        }
-        const uint32_t ia = wave_scan_u32(sa);
-        if (lane == kWave - 1) wtot[wave] = ia;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kScanWaves; ++w) {
-            const uint32_t x = wtot[w];
-            if (w < wave) before += x;
-            all += x;
-        }
-        __syncthreads();  // wtot is rewritten by the next chunk
-        uint32_t ea = carry + before + (ia - sa);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            if (first + q < NB) bsum[first + q] = ea;
-            ea += a[q];
-        }
-        carry += all;
-    }
-    if (t == 0) {
-        *total_a = carry;
-        *total_b = carry;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_md_offsets(uint32_t *__restrict__ cursor, uint32_t C, const uint32_t *__restrict__ bsum,
-                                                        uint32_t *__restrict__ start) {
-    __shared__ uint32_t wtot[kWaves];
-    const uint32_t c = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const uint32_t n = c < C ? cursor[c] : 0u;
-    const uint32_t in = wave_scan_u32(n);
-    if (lane == kWave - 1) wtot[wave] = in;
-    __syncthreads();
-    uint32_t base = bsum[blockIdx.x];
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) {
-        if (w < wave) base += wtot[w];
-    }
-    if (c < C) {
-        start[c] = base + (in - n);
-        cursor[c] = base + (in - n);
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_md_fill(const float *__restrict__ vertices, const int32_t *__restrict__ triangles, uint32_t T,
@@ -369,14 +258,6 @@ int check_args(uint32_t T, uint32_t G, const void *workspace, size_t workspace_b
     return PVD_OK;
 }
 
-int check_memset(hipError_t e) {
-    if (e != hipSuccess) {
-        set_last_error(e);
-        return PVD_ERR_LAUNCH;
-    }
-    return PVD_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -401,11 +282,11 @@ int pvd_mesh_dist_build(const float *vertices, uint32_t V, const int32_t *triang
     if ((rc = check_memset(hipMemsetAsync(cursor, 0, 4 * (size_t)C, st))) != PVD_OK) return rc;
     hipLaunchKernelGGL(k_md_count, dim3(TB), dim3(kThreads), 0, st, vertices, V, triangles, T, bmin3, bmax3, G, header, cursor, tcell);
     if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_md_blocksum, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum);
+    hipLaunchKernelGGL(k_blocksum<uint32_t>, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum);
     if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_md_scan, dim3(1), dim3(kScanThreads), 0, st, bsum, NB, start + C, header + 7);
+    hipLaunchKernelGGL(k_scan<uint32_t>, dim3(1), dim3(kScanThreads), 0, st, bsum, NB, start + C, header + 7);
     if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_md_offsets, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum, start);
+    hipLaunchKernelGGL(k_offsets<uint32_t>, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum, start);
     if ((rc = check_launch()) != PVD_OK) return rc;
     if (T == 0) return PVD_OK;
     hipLaunchKernelGGL(k_md_fill, dim3(TB), dim3(kThreads), 0, st, vertices, triangles, T, tcell, cursor, packed);

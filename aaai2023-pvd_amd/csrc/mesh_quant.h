@@ -2,14 +2,9 @@
 // box), shared by csrc/mesh_simplify.hip and csrc/mesh_smooth.hip so that both quantise with the same instructions.
 #pragma once
 
-#include "pvd_device.h"
+#include "mesh_grid.h"
 
 namespace pvd {
-
-// the pure parts are __host__ __device__: a CPU build can walk the same code
-#define PVD_HD __host__ __device__ __forceinline__
-
-PVD_HD bool finite1(float x) { return fabsf(x) < INFINITY; }  // false for NaN
 
 struct Box {  // per axis: the origin, the extent, whether the axis is flat
     double lo[3], ext[3];

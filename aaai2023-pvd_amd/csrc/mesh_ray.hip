@@ -5,12 +5,14 @@
 //                wave on each of the two 64-bit totals.
 // k_mr_bin       one lane per triangle: the packed record (index -1: invalid), one integer atomicAdd per cell of its range on the
 //                cell's count, or a slot of the outside list.
-// k_mr_blocksum, k_mr_scan, k_mr_offsets   the per-cell counts -> the cell starts, as in csrc/mesh_dist.hip.
+// k_blocksum, k_scan, k_offsets   (csrc/block_scan.h) the per-cell counts -> the cell starts and fill cursors; the
+//                total (the number of pairs) to start[C] and to the header.
 // k_mr_fill      one lane per triangle: per cell of its range a slot from the cell's cursor (integer atomicAdd), its index into it.
 // k_mr_cast      one lane per ray: clip, walk, outside list.  No LDS, no atomics.
 // No workgroup waits on another one of the same launch, and no loop retries an atomic.  The order of the pairs inside a cell depends
 // on the run; the cast's (t, index) minimum does not.
-#include "pvd_device.h"
+#include "block_scan.h"
+#include "mesh_grid.h"
 
 #include "../../include/pvd_hip_mesh_ray.h"
 
@@ -18,12 +20,6 @@ namespace {
 
 using namespace pvd;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kScanThreads = 1024;
-constexpr int kScanWaves = kScanThreads / kWave;
-constexpr int kScanItems = 8;
-constexpr uint32_t kScanChunk = kScanThreads * kScanItems;
 constexpr uint32_t kMaxT = 0x7fffffffu;
 constexpr uint64_t kMaxPairs = 0x7fffffffull;
 
@@ -47,12 +43,7 @@ inline Layout layout(uint32_t T, uint32_t G, uint64_t pairs) {
     return l;
 }
 
-// the pure parts (box, ranges, the test, the walk) are __host__ __device__: a CPU build can walk the same code
-#define PVD_HD __host__ __device__ __forceinline__
-
-PVD_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
-PVD_HD uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
-PVD_HD uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
+// the pure parts (box, ranges, the test, the walk) are PVD_HD, __host__ __device__: a CPU build can walk the same code
 PVD_HD float sel3(float x, float y, float z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
 
 struct Box {  // per axis: flat (one layer from -inf to +inf), the bounds, the cell size and its inverse, the dilation eps
@@ -75,16 +66,6 @@ PVD_HD Box box_of(const float *__restrict__ bmin3, const float *__restrict__ bma
         b.eps[a] = ok ? 0x1p-20 * ext : 0.0;
     }
     return b;
-}
-
-// the cell coordinate of x along axis a: one monotone function of x, used for the triangles' ranges and for the rays' start alike
-PVD_HD int cell_axis(const Box &b, int a, double x, uint32_t G) {
-    const double v = (x - b.lo[a]) * b.inv_h[a];
-    return v >= 1.0 ? (int)fmin(v, (double)(G - 1)) : 0;  // NaN and everything below 1 -> 0; a flat axis -> 0
-}
-
-PVD_HD bool finite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for NaN
 }
 
 enum : int { kInvalid = 0, kInside = 1, kOutside = 2 };
@@ -116,22 +97,6 @@ PVD_HD int classify(const float *__restrict__ vertices, uint32_t V, const int32_
     return inside ? kInside : kOutside;
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-    return v;
-}
-// inclusive scan over the wave
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t w = __shfl_up(v, o, kWave);
-        if (lane >= (uint32_t)o) v += w;
-    }
-    return v;
-}
-
 // a triangle's range holds at most 2^24 cells and a wave 64 triangles: the wave's sum fits 32 bits, the totals are 64 bits wide
 __global__ __launch_bounds__(kThreads) void k_mr_count(const float *__restrict__ vertices, uint32_t V, const int32_t *__restrict__ triangles,
                                                       uint32_t T, const float *__restrict__ bmin3, const float *__restrict__ bmax3, uint32_t G,
@@ -145,8 +110,8 @@ __global__ __launch_bounds__(kThreads) void k_mr_count(const float *__restrict__
         if (cls == kInside) cells = (uint32_t)(k1[0] - k0[0] + 1) * (uint32_t)(k1[1] - k0[1] + 1) * (uint32_t)(k1[2] - k0[2] + 1);
         out = cls == kOutside ? 1u : 0u;
     }
-    cells = wave_sum_u32(cells);
-    out = wave_sum_u32(out);
+    cells = wave_sum(cells);
+    out = wave_sum(out);
     if ((threadIdx.x & (kWave - 1)) == 0) {
         if (cells) atomicAdd(&totals[0], (unsigned long long)cells);
         if (out) atomicAdd(&totals[1], (unsigned long long)out);
@@ -178,78 +143,6 @@ __global__ __launch_bounds__(kThreads) void k_mr_bin(const float *__restrict__ v
     } else if (cls == kOutside) {
         const uint32_t slot = atomicAdd(&header[0], 1u);
         if (slot < T) outside[slot] = t;  // (always: at most T triangles are outside)
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_mr_blocksum(const uint32_t *__restrict__ cursor, uint32_t C, uint32_t *__restrict__ bsum) {
-    __shared__ uint32_t red[kWaves];
-    const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-    const uint32_t s = wave_sum_u32(c < C ? cursor[c] : 0u);
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) a += red[w];
-        bsum[blockIdx.x] = a;
-    }
-}
-
-// one workgroup; sums [NB] -> exclusive scan in place; the total to total_a and total_b
-__global__ __launch_bounds__(kScanThreads) void k_mr_scan(uint32_t *__restrict__ bsum, uint32_t NB, uint32_t *__restrict__ total_a,
-                                                         uint32_t *__restrict__ total_b) {
-    __shared__ uint32_t wtot[kScanWaves];
-    const uint32_t t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < NB; base += kScanChunk) {  // the trip count is the same for every thread
-        const uint32_t first = base + t * kScanItems;
-        uint32_t a[kScanItems], sa = 0;
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            a[q] = first + q < NB ? bsum[first + q] : 0u;
-            sa += a[q];
-        }
-        const uint32_t ia = wave_scan_u32(sa);
-        if (lane == kWave - 1) wtot[wave] = ia;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kScanWaves; ++w) {
-            const uint32_t x = wtot[w];
-            if (w < wave) before += x;
-            all += x;
-        }
-        __syncthreads();  // wtot is rewritten by the next chunk
-        uint32_t ea = carry + before + (ia - sa);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            if (first + q < NB) bsum[first + q] = ea;
-            ea += a[q];
-        }
-        carry += all;
-    }
-    if (t == 0) {
-        *total_a = carry;
-        *total_b = carry;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_mr_offsets(uint32_t *__restrict__ cursor, uint32_t C, const uint32_t *__restrict__ bsum,
-                                                        uint32_t *__restrict__ start) {
-    __shared__ uint32_t wtot[kWaves];
-    const uint32_t c = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const uint32_t n = c < C ? cursor[c] : 0u;
-    const uint32_t in = wave_scan_u32(n);
-    if (lane == kWave - 1) wtot[wave] = in;
-    __syncthreads();
-    uint32_t base = bsum[blockIdx.x];
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) {
-        if (w < wave) base += wtot[w];
-    }
-    if (c < C) {
-        start[c] = base + (in - n);
-        cursor[c] = base + (in - n);
     }
 }
 
@@ -454,14 +347,6 @@ int check_args(uint32_t T, uint32_t G, uint64_t pairs, const void *workspace, si
     return PVD_OK;
 }
 
-int check_memset(hipError_t e) {
-    if (e != hipSuccess) {
-        set_last_error(e);
-        return PVD_ERR_LAUNCH;
-    }
-    return PVD_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -497,11 +382,11 @@ int pvd_mesh_ray_build(const float *vertices, uint32_t V, const int32_t *triangl
     if ((rc = check_memset(hipMemsetAsync(cursor, 0, 4 * (size_t)C, st))) != PVD_OK) return rc;
     hipLaunchKernelGGL(k_mr_bin, dim3(TB), dim3(kThreads), 0, st, vertices, V, triangles, T, bmin3, bmax3, G, header, cursor, outside, packed);
     if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_mr_blocksum, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum);
+    hipLaunchKernelGGL(k_blocksum<uint32_t>, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum);
     if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_mr_scan, dim3(1), dim3(kScanThreads), 0, st, bsum, NB, start + C, header + 7);
+    hipLaunchKernelGGL(k_scan<uint32_t>, dim3(1), dim3(kScanThreads), 0, st, bsum, NB, start + C, header + 7);
     if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_mr_offsets, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum, start);
+    hipLaunchKernelGGL(k_offsets<uint32_t>, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum, start);
     if ((rc = check_launch()) != PVD_OK) return rc;
     if (T == 0) return PVD_OK;
     hipLaunchKernelGGL(k_mr_fill, dim3(TB), dim3(kThreads), 0, st, vertices, V, triangles, T, header, G, (uint32_t)pairs, cursor, list);

@@ -5,17 +5,17 @@
 // k_ms_cells     one lane per vertex: its cell (all-ones for a vertex that is not valid), kept for the three kernels that need it.
 // k_ms_tris      one lane per triangle: the survive flag, and a plain store of 1 into the flag word of each of its three cells
 //                (every writer of a word stores the same value).
-// k_ms_blocksum  one lane per word: the sum of the workgroup's 256 flags (cells, then triangles).
-// k_ms_scan      ONE workgroup walks those sums in chunks of 8192 with a running carry: exclusive scan in place, the total to
-//                totals_dev.
+// k_blocksum, k_scan   (csrc/block_scan.h) the sums of the flags per workgroup (cells, then triangles) and their scan; the
+//                total to totals_dev.
 // k_ms_offsets   one lane per word: the flag becomes its exclusive rank (the cell's new index, the triangle's output row), all-ones
 //                where the flag was 0.
 // emit phase
 // k_ms_gather    one lane per vertex: vertex_map, and 64-bit integer atomicAdd of (1, q, attributes) into the kept cell's row.
 // k_ms_finish    one lane per new vertex: the means, mapped back into the box.
 // k_ms_remap     one lane per triangle: a survivor writes its remapped row at its rank.
-// The same count -> one-block scan -> offsets shape as csrc/mesh.hip and csrc/mesh_dist.hip: no workgroup waits on another one of
-// the same launch, and no loop retries an atomic.
+// The count -> one-workgroup scan -> offsets shape of csrc/block_scan.h: no workgroup waits on another one of the same launch, and
+// no loop retries an atomic.
+#include "block_scan.h"
 #include "mesh_quant.h"
 
 #include "../../include/pvd_hip_mesh_simplify.h"
@@ -24,12 +24,6 @@ namespace {
 
 using namespace pvd;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kScanThreads = 1024;
-constexpr int kScanWaves = kScanThreads / kWave;
-constexpr int kScanItems = 8;
-constexpr uint32_t kScanChunk = kScanThreads * kScanItems;
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t kMaxN = 0x7fffffffu;  // V and T
 constexpr int kMaxK = PVD_MESH_SIMPLIFY_MAX_K;
@@ -58,7 +52,7 @@ inline bool in_limits(uint32_t V, uint32_t T, uint32_t G, uint32_t K) {
     return G >= 1 && G <= PVD_MESH_SIMPLIFY_MAX_G && K <= (uint32_t)kMaxK && V <= kMaxN && T <= kMaxN;
 }
 
-// finite1, Box, box_of and quantise (q_a) are in mesh_quant.h
+// Box, box_of and quantise (q_a) are in mesh_quant.h, finite1 in mesh_grid.h
 
 PVD_HD uint32_t cell_axis(int64_t q, uint32_t G) {
     const uint32_t k = (uint32_t)(((uint64_t)q * G) >> 30);
@@ -69,22 +63,6 @@ PVD_HD uint32_t cell_axis(int64_t q, uint32_t G) {
 PVD_HD int64_t quantise_attr(float v) {
     if (!finite1(v)) return 0;
     return (int64_t)llrint(fmin(1.0, fmax(-1.0, (double)v)) * 0x1p30);
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-    return v;
-}
-// inclusive scan over the wave
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t w = __shfl_up(v, o, kWave);
-        if (lane >= (uint32_t)o) v += w;
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(kThreads) void k_ms_cells(const float *__restrict__ vertices, uint32_t V, const float *__restrict__ bmin3,
@@ -120,69 +98,13 @@ __global__ __launch_bounds__(kThreads) void k_ms_tris(const int32_t *__restrict_
     trow[t] = survives;
 }
 
-__global__ __launch_bounds__(kThreads) void k_ms_blocksum(const uint32_t *__restrict__ flag, uint32_t N, uint32_t *__restrict__ bsum) {
-    __shared__ uint32_t red[kWaves];
-    const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-    const uint32_t s = wave_sum_u32(c < N ? flag[c] : 0u);
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) a += red[w];
-        bsum[blockIdx.x] = a;
-    }
-}
-
-// one workgroup; sums [NB] -> exclusive scan in place; the total to *total
-__global__ __launch_bounds__(kScanThreads) void k_ms_scan(uint32_t *__restrict__ bsum, uint32_t NB, int32_t *__restrict__ total) {
-    __shared__ uint32_t wtot[kScanWaves];
-    const uint32_t t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < NB; base += kScanChunk) {  // the trip count is the same for every thread
-        const uint32_t first = base + t * kScanItems;
-        uint32_t a[kScanItems], sa = 0;
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            a[q] = first + q < NB ? bsum[first + q] : 0u;
-            sa += a[q];
-        }
-        const uint32_t ia = wave_scan_u32(sa);
-        if (lane == kWave - 1) wtot[wave] = ia;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kScanWaves; ++w) {
-            const uint32_t x = wtot[w];
-            if (w < wave) before += x;
-            all += x;
-        }
-        __syncthreads();  // wtot is rewritten by the next chunk
-        uint32_t ea = carry + before + (ia - sa);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            if (first + q < NB) bsum[first + q] = ea;
-            ea += a[q];
-        }
-        carry += all;
-    }
-    if (t == 0) *total = (int32_t)carry;  // at most 2^31 - 1 triangles, at most 2^27 cells
-}
-
 // flag (0 / 1) -> its exclusive rank where it was 1, kNone where it was 0; in place, each lane its own word
 __global__ __launch_bounds__(kThreads) void k_ms_offsets(uint32_t *__restrict__ flag, uint32_t N, const uint32_t *__restrict__ bsum) {
     __shared__ uint32_t wtot[kWaves];
-    const uint32_t c = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
     const uint32_t n = c < N ? flag[c] : 0u;
-    const uint32_t in = wave_scan_u32(n);
-    if (lane == kWave - 1) wtot[wave] = in;
-    __syncthreads();
-    uint32_t base = bsum[blockIdx.x];
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) {
-        if (w < wave) base += wtot[w];
-    }
-    if (c < N) flag[c] = n ? base + (in - n) : kNone;
+    const uint32_t rank = bsum[blockIdx.x] + block_exclusive(n, wtot);
+    if (c < N) flag[c] = n ? rank : kNone;
 }
 
 // acc: per new vertex 4 + K words of 64 bits -- n, S_x, S_y, S_z, A_0 .. A_{K-1}.  Two's complement: the unsigned add is the signed one.
@@ -249,23 +171,16 @@ int check_args(uint32_t V, uint32_t T, uint32_t G, uint32_t K, const void *works
     return PVD_OK;
 }
 
-int check_memset(hipError_t e) {
-    if (e != hipSuccess) {
-        set_last_error(e);
-        return PVD_ERR_LAUNCH;
-    }
-    return PVD_OK;
-}
-
 // blocksum -> scan -> offsets over the N flags at `flag`
 int scan_flags(uint32_t *flag, uint32_t N, uint32_t *bsum, int32_t *total, hipStream_t st) {
     const uint32_t NB = div_up(N, kThreads);
     int rc;
     if (NB) {
-        hipLaunchKernelGGL(k_ms_blocksum, dim3(NB), dim3(kThreads), 0, st, flag, N, bsum);
+        hipLaunchKernelGGL(k_blocksum<uint32_t>, dim3(NB), dim3(kThreads), 0, st, flag, N, bsum);
         if ((rc = check_launch()) != PVD_OK) return rc;
     }
-    hipLaunchKernelGGL(k_ms_scan, dim3(1), dim3(kScanThreads), 0, st, bsum, NB, total);  // NB == 0: the total 0
+    // NB == 0: the total 0.  The total is at most 2^31 - 1 triangles or 2^27 cells: the unsigned word is the signed one.
+    hipLaunchKernelGGL(k_scan<uint32_t>, dim3(1), dim3(kScanThreads), 0, st, bsum, NB, (uint32_t *)total, (uint32_t *)total);
     if ((rc = check_launch()) != PVD_OK) return rc;
     if (NB) {
         hipLaunchKernelGGL(k_ms_offsets, dim3(NB), dim3(kThreads), 0, st, flag, N, bsum);

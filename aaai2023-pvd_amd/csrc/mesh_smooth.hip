@@ -5,8 +5,8 @@
 // k_sm_quant     one lane per vertex: its 16-byte row (q_x, q_y, q_z, flags), zeros and no valid flag for a vertex that is not valid.
 // k_sm_count     one lane per triangle: a valid one adds 2 to the row size of each of its corners (32-bit integer atomicAdd).
 // k_sm_blocksum  one lane per vertex: the sum (64-bit) and the largest of the workgroup's 256 row sizes.
-// k_sm_scan      ONE workgroup walks those sums in chunks of 8192 with a running carry: exclusive scan in place; the total and the
-//                largest row to totals_dev, the total also behind the last row offset.
+// k_sm_scan      ONE workgroup: the exclusive scan of those sums in place (scan_sums, csrc/block_scan.h) and the largest of the
+//                maxima; the total and the largest row to totals_dev, the total also behind the last row offset.
 // k_sm_offsets   one lane per vertex: its 64-bit row offset, and its index appended to the list of long rows (one atomic counter)
 //                when it is movable and its row is longer than kLongRow.
 // k_sm_fill      one lane per triangle: a valid one takes two slots of each corner's row by an atomicSub of 2 on the row size -- the
@@ -17,8 +17,9 @@
 //                from the list, one wave per row, grid-strided: the lanes stride the row, and three int64 partial sums are reduced
 //                across the 64 lanes.  A long row is written by that wave's lane 0 alone.
 // k_sm_out       one lane per vertex: a movable vertex mapped back into the box, any other one its input bits.
-// The same count -> one-block scan -> offsets shape as csrc/mesh_simplify.hip: no workgroup waits on another one of the same launch,
-// and no loop retries an atomic.  The dependency between two passes is the launch boundary.
+// The count -> one-workgroup scan -> offsets shape of csrc/block_scan.h, over 64-bit sums: no workgroup waits on another one of the
+// same launch, and no loop retries an atomic.  The dependency between two passes is the launch boundary.
+#include "block_scan.h"
 #include "mesh_quant.h"
 
 #include "../../include/pvd_hip_mesh_smooth.h"
@@ -27,12 +28,6 @@ namespace {
 
 using namespace pvd;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kScanThreads = 1024;
-constexpr int kScanWaves = kScanThreads / kWave;
-constexpr int kScanItems = 8;
-constexpr uint32_t kScanChunk = kScanThreads * kScanItems;
 constexpr uint32_t kMaxN = 0x7fffffffu;  // V and T
 // A movable row of more than kLongRow entries is summed by a whole wavefront, any other one by a single lane.  One wave stride is 64
 // entries; a closed manifold mesh has rows of about 12.  Not A/B-measured: profiles/mesh_smooth.txt says what was.
@@ -62,30 +57,6 @@ inline Layout layout(uint32_t V, uint32_t T) {
 }
 
 inline bool in_limits(uint32_t V, uint32_t T) { return V <= kMaxN && T <= kMaxN; }
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, o, kWave);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const uint32_t w = __shfl_down(v, o, kWave);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-// inclusive scan over the wave
-__device__ __forceinline__ uint64_t wave_scan_u64(uint64_t v) {
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint64_t w = (uint64_t)__shfl_up((unsigned long long)v, o, kWave);
-        if (lane >= (uint32_t)o) v += w;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void k_sm_quant(const float *__restrict__ vertices, uint32_t V, const float *__restrict__ bmin3,
                                                       const float *__restrict__ bmax3, const uint8_t *__restrict__ pinned,
@@ -131,21 +102,9 @@ __global__ __launch_bounds__(kThreads) void k_sm_blocksum(const uint32_t *__rest
     __shared__ uint32_t big[kWaves];
     const uint32_t v = blockIdx.x * kThreads + threadIdx.x;
     const uint32_t n = v < V ? cnt[v] : 0u;
-    const uint64_t s = wave_sum_u64(n);
-    const uint32_t m = wave_max_u32(n);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        red[threadIdx.x / kWave] = s;
-        big[threadIdx.x / kWave] = m;
-    }
-    __syncthreads();
+    const uint64_t a = block_sum((uint64_t)n, red);
+    const uint32_t b = block_max(n, big);
     if (threadIdx.x == 0) {
-        uint64_t a = 0;
-        uint32_t b = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            a += red[w];
-            b = big[w] > b ? big[w] : b;
-        }
         bsum[blockIdx.x] = a;
         bmax[blockIdx.x] = b;
     }
@@ -154,50 +113,15 @@ __global__ __launch_bounds__(kThreads) void k_sm_blocksum(const uint32_t *__rest
 // one workgroup; sums [NB] -> exclusive scan in place; (total, largest row) to totals, the total to *last_off
 __global__ __launch_bounds__(kScanThreads) void k_sm_scan(uint64_t *__restrict__ bsum, const uint32_t *__restrict__ bmax, uint32_t NB,
                                                          int64_t *__restrict__ totals, uint64_t *__restrict__ last_off) {
-    __shared__ uint64_t wtot[kScanWaves];
     __shared__ uint32_t wbig[kScanWaves];
-    const uint32_t t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-    uint64_t carry = 0;
+    const uint64_t total = scan_sums(bsum, NB);
     uint32_t big = 0;
-    for (uint32_t base = 0; base < NB; base += kScanChunk) {  // the trip count is the same for every thread
-        const uint32_t first = base + t * kScanItems;
-        uint64_t a[kScanItems], sa = 0;
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            const bool in = first + q < NB;
-            a[q] = in ? bsum[first + q] : 0u;
-            const uint32_t m = in ? bmax[first + q] : 0u;
-            big = m > big ? m : big;
-            sa += a[q];
-        }
-        const uint64_t ia = wave_scan_u64(sa);
-        if (lane == kWave - 1) wtot[wave] = ia;
-        __syncthreads();
-        uint64_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kScanWaves; ++w) {
-            const uint64_t x = wtot[w];
-            if (w < wave) before += x;
-            all += x;
-        }
-        __syncthreads();  // wtot is rewritten by the next chunk
-        uint64_t ea = carry + before + (ia - sa);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            if (first + q < NB) bsum[first + q] = ea;
-            ea += a[q];
-        }
-        carry += all;
-    }
-    big = wave_max_u32(big);
-    if (lane == 0) wbig[wave] = big;
-    __syncthreads();
-    if (t == 0) {
-#pragma unroll
-        for (int w = 0; w < kScanWaves; ++w) big = wbig[w] > big ? wbig[w] : big;
-        totals[0] = (int64_t)carry;  // at most 6 (2^31 - 1)
+    for (uint32_t i = threadIdx.x; i < NB; i += kScanThreads) big = bmax[i] > big ? bmax[i] : big;  // (no barrier in this loop)
+    big = block_max(big, wbig);
+    if (threadIdx.x == 0) {
+        totals[0] = (int64_t)total;  // at most 6 (2^31 - 1)
         totals[1] = (int64_t)big;
-        *last_off = carry;
+        *last_off = total;
     }
 }
 
@@ -205,18 +129,11 @@ __global__ __launch_bounds__(kThreads) void k_sm_offsets(const uint32_t *__restr
                                                         const int4 *__restrict__ q0, uint64_t *__restrict__ off,
                                                         uint32_t *__restrict__ longs, uint32_t *__restrict__ nlong) {
     __shared__ uint64_t wtot[kWaves];
-    const uint32_t v = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const uint32_t v = blockIdx.x * kThreads + threadIdx.x;
     const uint32_t n = v < V ? cnt[v] : 0u;
-    const uint64_t in = wave_scan_u64(n);
-    if (lane == kWave - 1) wtot[wave] = in;
-    __syncthreads();
-    uint64_t base = bsum[blockIdx.x];
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) {
-        if (w < wave) base += wtot[w];
-    }
+    const uint64_t at = bsum[blockIdx.x] + block_exclusive((uint64_t)n, wtot);
     if (v >= V) return;
-    off[v] = base + (in - n);
+    off[v] = at;
     if (n > kLongRow && ((uint32_t)q0[v].w & (kValid | kPinned)) == kValid) longs[atomicAdd(nlong, 1u)] = v;  // at most V of them
 }
 
@@ -287,9 +204,9 @@ __global__ __launch_bounds__(kThreads) void k_sm_pass(const int4 *__restrict__ s
                 sz += o.z;
             }
         }
-        sx = (int64_t)wave_sum_u64((uint64_t)sx);  // two's complement: the unsigned sum is the signed one
-        sy = (int64_t)wave_sum_u64((uint64_t)sy);
-        sz = (int64_t)wave_sum_u64((uint64_t)sz);
+        sx = (int64_t)wave_sum((uint64_t)sx);  // two's complement: the unsigned sum is the signed one
+        sy = (int64_t)wave_sum((uint64_t)sy);
+        sz = (int64_t)wave_sum((uint64_t)sz);
         if (lane == 0 && n > kLongRow) {
             const int4 me = src[r];
             const double nd = (double)n;
@@ -328,14 +245,6 @@ int check_args(uint32_t V, uint32_t T, const void *workspace, size_t workspace_b
     if (!workspace || ((uintptr_t)workspace & 15u)) return PVD_ERR_INVALID;
     if (!in_limits(V, T)) return PVD_ERR_UNSUPPORTED;
     if (workspace_bytes < layout(V, T).total) return PVD_ERR_INVALID;
-    return PVD_OK;
-}
-
-int check_memset(hipError_t e) {
-    if (e != hipSuccess) {
-        set_last_error(e);
-        return PVD_ERR_LAUNCH;
-    }
     return PVD_OK;
 }
 

@@ -33,6 +33,15 @@ inline int check_launch() {
     return PVD_OK;
 }
 
+// the status of a hipMemsetAsync (or any call that returns its error)
+inline int check_memset(hipError_t e) {
+    if (e != hipSuccess) {
+        set_last_error(e);
+        return PVD_ERR_LAUNCH;
+    }
+    return PVD_OK;
+}
+
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
 __device__ __forceinline__ float sign1f(float x) { return copysignf(1.0f, x); }
 

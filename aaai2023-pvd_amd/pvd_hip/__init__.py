@@ -1728,6 +1728,28 @@ def components_neighbours():
     return [tuple(buf[3 * q:3 * q + 3]) for q in range(n)]
 
 
+# --------------------------------------------------------------------------- checks the mesh bindings below share
+def _mesh_and_box(vertices, triangles, bmin, bmax):
+    """vertices [V,3] f32, triangles [T,3] int32 (None where the call takes T as a number), bmin / bmax 3 floats each -> (V, T)."""
+    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
+    if triangles is not None:
+        _want(triangles, torch.int32, "triangles")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or (triangles is not None and (triangles.dim() != 2 or triangles.shape[1] != 3)):
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    return int(vertices.shape[0]), None if triangles is None else int(triangles.shape[0])
+
+
+def _mesh_workspace(workspace, need, size_fn):
+    """workspace: uint8, at least `need` bytes (what the call `size_fn` returns), 16-byte aligned."""
+    _want(workspace, torch.uint8, "workspace")
+    if workspace.numel() < need:
+        raise PvdHipError("workspace too small: %s bytes are needed" % size_fn)
+    if workspace.data_ptr() % 16:
+        raise PvdHipError("workspace must be 16-byte aligned")
+
+
 # --------------------------------------------------------------------------- point-to-mesh distance (include/pvd_hip_mesh_dist.h)
 MESH_DIST_MAX_G = 256  # PVD_MESH_DIST_MAX_G: cells per axis, 1 .. 256
 
@@ -1741,27 +1763,13 @@ def mesh_dist_workspace_bytes(T, G):
     return n
 
 
-def _mesh_dist_workspace(workspace, T, G):
-    _want(workspace, torch.uint8, "workspace")
-    if workspace.numel() < mesh_dist_workspace_bytes(T, G):
-        raise PvdHipError("workspace too small: mesh_dist_workspace_bytes(T, G) bytes are needed")
-    if workspace.data_ptr() % 16:
-        raise PvdHipError("workspace must be 16-byte aligned")
-
-
 def mesh_dist_build(vertices, triangles, bmin, bmax, G, workspace):
     """pvd_mesh_dist_build: bins the valid triangles of the mesh (vertices [V,3] f32, triangles [T,3] int32) into G^3 cells over the
     box bmin .. bmax (device f32 [3] each) and leaves in the workspace (uint8, mesh_dist_workspace_bytes(T, G)) what mesh_dist_query
     needs."""
     dev = _dev(vertices, triangles, bmin, bmax, workspace)
-    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
-    _want(triangles, torch.int32, "triangles")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
-    if bmin.numel() < 3 or bmax.numel() < 3:
-        raise PvdHipError("bmin / bmax must hold 3 floats")
-    V, T = int(vertices.shape[0]), int(triangles.shape[0])
-    _mesh_dist_workspace(workspace, T, G)
+    V, T = _mesh_and_box(vertices, triangles, bmin, bmax)
+    _mesh_workspace(workspace, mesh_dist_workspace_bytes(T, G), "mesh_dist_workspace_bytes(T, G)")
     _call("pvd_mesh_dist_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _p(workspace),
           ctypes.c_size_t(workspace.numel()))
 
@@ -1781,7 +1789,7 @@ def mesh_dist_query(points, T, G, workspace, max_dist, dist, tri):
     max_dist = float(max_dist)
     if not (0.0 < max_dist < float("inf")):
         raise PvdHipError("max_dist must be finite and > 0")
-    _mesh_dist_workspace(workspace, T, G)
+    _mesh_workspace(workspace, mesh_dist_workspace_bytes(T, G), "mesh_dist_workspace_bytes(T, G)")
     _call("pvd_mesh_dist_query", dev, _p(points), _u32(N), _u32(T), _u32(G), _p(workspace), ctypes.c_size_t(workspace.numel()),
           _f32(max_dist), _p(dist), _p(tri))
 
@@ -1803,17 +1811,8 @@ def mesh_simplify_workspace_bytes(V, T, G, K):
 
 
 def _mesh_simplify_common(vertices, triangles, bmin, bmax, G, K, workspace):
-    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
-    _want(triangles, torch.int32, "triangles"), _want(workspace, torch.uint8, "workspace")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
-    if bmin.numel() < 3 or bmax.numel() < 3:
-        raise PvdHipError("bmin / bmax must hold 3 floats")
-    V, T = int(vertices.shape[0]), int(triangles.shape[0])
-    if workspace.numel() < mesh_simplify_workspace_bytes(V, T, G, K):
-        raise PvdHipError("workspace too small: mesh_simplify_workspace_bytes(V, T, G, K) bytes are needed")
-    if workspace.data_ptr() % 16:
-        raise PvdHipError("workspace must be 16-byte aligned")
+    V, T = _mesh_and_box(vertices, triangles, bmin, bmax)
+    _mesh_workspace(workspace, mesh_simplify_workspace_bytes(V, T, G, K), "mesh_simplify_workspace_bytes(V, T, G, K)")
     return V, T
 
 
@@ -1875,24 +1874,11 @@ def mesh_ray_workspace_bytes(T, G, pairs):
     return n
 
 
-def _mesh_ray_workspace(workspace, T, G, pairs):
-    _want(workspace, torch.uint8, "workspace")
-    if workspace.numel() < mesh_ray_workspace_bytes(T, G, pairs):
-        raise PvdHipError("workspace too small: mesh_ray_workspace_bytes(T, G, pairs) bytes are needed")
-    if workspace.data_ptr() % 16:
-        raise PvdHipError("workspace must be 16-byte aligned")
-
-
 def _mesh_ray_mesh(vertices, triangles, bmin, bmax, G):
-    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
-    _want(triangles, torch.int32, "triangles")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
-    if bmin.numel() < 3 or bmax.numel() < 3:
-        raise PvdHipError("bmin / bmax must hold 3 floats")
+    V, T = _mesh_and_box(vertices, triangles, bmin, bmax)
     if not 1 <= int(G) <= MESH_RAY_MAX_G:
         raise PvdHipError("G must be 1 .. %d, got %d" % (MESH_RAY_MAX_G, int(G)))
-    return int(vertices.shape[0]), int(triangles.shape[0])
+    return V, T
 
 
 def mesh_ray_count(vertices, triangles, bmin, bmax, G, totals):
@@ -1911,7 +1897,7 @@ def mesh_ray_build(vertices, triangles, bmin, bmax, G, pairs, workspace):
     in the workspace (uint8, mesh_ray_workspace_bytes(T, G, pairs)) what mesh_ray_cast needs."""
     dev = _dev(vertices, triangles, bmin, bmax, workspace)
     V, T = _mesh_ray_mesh(vertices, triangles, bmin, bmax, G)
-    _mesh_ray_workspace(workspace, T, G, pairs)
+    _mesh_workspace(workspace, mesh_ray_workspace_bytes(T, G, pairs), "mesh_ray_workspace_bytes(T, G, pairs)")
     _call("pvd_mesh_ray_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _u64(pairs), _p(workspace),
           ctypes.c_size_t(workspace.numel()))
 
@@ -1932,7 +1918,7 @@ def mesh_ray_cast(origins, dirs, T, G, pairs, workspace, t_min, t_max, t, tri, b
     t_min, t_max = float(t_min), float(t_max)
     if not (0.0 <= t_min < float("inf")) or not t_max > t_min:
         raise PvdHipError("t_min must be finite and >= 0 and t_max > t_min")
-    _mesh_ray_workspace(workspace, T, G, pairs)
+    _mesh_workspace(workspace, mesh_ray_workspace_bytes(T, G, pairs), "mesh_ray_workspace_bytes(T, G, pairs)")
     _call("pvd_mesh_ray_cast", dev, _p(origins), _p(dirs), _u32(N), _u32(T), _u32(G), _u64(pairs), _p(workspace),
           ctypes.c_size_t(workspace.numel()), _f32(t_min), _f32(t_max), _p(t), _p(tri), _p(bary))
 
@@ -1951,17 +1937,8 @@ def mesh_smooth_workspace_bytes(V, T):
 
 
 def _mesh_smooth_common(vertices, T, bmin, bmax, workspace):
-    _f32_all(vertices=vertices, bmin=bmin, bmax=bmax)
-    _want(workspace, torch.uint8, "workspace")
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise PvdHipError("vertices must be [V,3]")
-    if bmin.numel() < 3 or bmax.numel() < 3:
-        raise PvdHipError("bmin / bmax must hold 3 floats")
-    V = int(vertices.shape[0])
-    if workspace.numel() < mesh_smooth_workspace_bytes(V, T):
-        raise PvdHipError("workspace too small: mesh_smooth_workspace_bytes(V, T) bytes are needed")
-    if workspace.data_ptr() % 16:
-        raise PvdHipError("workspace must be 16-byte aligned")
+    V, _ = _mesh_and_box(vertices, None, bmin, bmax)
+    _mesh_workspace(workspace, mesh_smooth_workspace_bytes(V, T), "mesh_smooth_workspace_bytes(V, T)")
     return V
 
 

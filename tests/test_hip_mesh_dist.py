@@ -144,6 +144,31 @@ def test_the_distance_is_the_restatements(kind, R, which, N):
     assert d2.cpu().numpy().tobytes() == dist.tobytes() and t2.cpu().numpy().tobytes() == tri.tobytes()
 
 
+def _centroid_cells(verts, tris, G, bmin=BMIN, bmax=BMAX):
+    """The x-major cell index of every triangle's centroid in the G^3 grid over the box, as include/pvd_hip_mesh_dist.h bins it."""
+    lo, hi = np.array(bmin, np.float64), np.array(bmax, np.float64)
+    m = verts.astype(np.float64)[tris].sum(axis=1) / 3.0
+    k = np.clip(np.floor((m - lo) * (G / (hi - lo))), 0, G - 1).astype(np.int64)
+    return (k[:, 0] * G + k[:, 1]) * G + k[:, 2]
+
+
+def test_the_scan_of_the_cell_counts_carries_into_a_second_chunk():
+    """G = 129: 2 146 689 cells are 8386 per-workgroup sums, one chunk of 8192 and a second one that starts from the first one's
+    carry; every cell from index 8192 * 256 on has its start from that carry.  The cell index is x-major, so that cell lies in the
+    x-layer 126 of 129: in the box of the other tests the sphere (x = -0.6 .. 0.6 of -1 .. 1) stays below it, so this box is the same one
+    stretched to x = -30, which puts x = 0 into that layer.  The reference does not depend on the box."""
+    G, lo, hi = 129, (-30.0,) + BMIN[1:], (0.7,) + BMAX[1:]
+    assert 8192 < -(-G ** 3 // 256) <= 2 * 8192
+    verts, tris = _mesh("sphere", 9)
+    cells = _centroid_cells(verts, tris, G, lo, hi)
+    assert (cells < 8192 * 256).sum() > 100 and (cells >= 8192 * 256).sum() > 100  # triangles on both sides of the chunk boundary
+    p, D, ref, _ = _reference("sphere", 9, "own", 257)
+    dist, tri = _query(p, verts, tris, G=G, bmin=lo, bmax=hi)
+    _compare("sphere R=9 own, G=129", p, verts, tris, dist, tri, D, ref)
+    d7, t7 = _query(p, verts, tris, G=7, bmin=lo, bmax=hi)
+    assert dist.tobytes() == d7.tobytes() and tri.tobytes() == t7.tobytes()
+
+
 # ------------------------------------------------------------------------------------------------------------- grid independence
 def _grid_independent(label, points, verts, tris, boxes, reference=None):
     base = None

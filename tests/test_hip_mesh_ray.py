@@ -123,6 +123,21 @@ def test_the_first_hit_is_the_restatements_bit_for_bit(kind, R, which, N):
     _same(tuple(a.cpu().numpy() for a in got), (rt, rtri, rbary), "%s R=%d %s, default box" % (kind, R, which))
 
 
+def test_the_scan_of_the_cell_counts_carries_into_a_second_chunk():
+    """G = 129: 2 146 689 cells are 8386 per-workgroup sums, one chunk of 8192 and a second one that starts from the first one's
+    carry.  The cell index is x-major, so cell 8192 * 256 lies in the x-layer 126 of 129: in the box of the other tests the sphere
+    (x = -0.6 .. 0.6 of -1 .. 1) stays below it, so this box is the same one stretched to x = -30, which puts x = 0 into that layer and
+    still holds the whole mesh.  The reference does not depend on the box."""
+    G, lo, hi = 129, (-30.0,) + BMIN[1:], (0.7,) + BMAX[1:]
+    assert 8192 < -(-G ** 3 // 256) <= 2 * 8192
+    verts, tris = _mesh("sphere", 9)
+    x = (verts.astype(np.float64)[:, 0][tris] - lo[0]) * (G / (hi[0] - lo[0]))  # [T,3]: the corners' x in cells
+    layer = 8192 * 256 // G ** 2
+    assert layer == 126 and (x.max(axis=1) < layer - 0.5).sum() > 50 and (x.min(axis=1) > layer + 1.5).sum() > 50  # both sides
+    o, d, _, rt, rtri, rbary = _reference("sphere", 9, "camera", 1000)
+    _same(_cast(o, d, verts, tris, G=G, bmin=lo, bmax=hi), (rt, rtri, rbary), "sphere R=9 camera, G=129")
+
+
 def test_the_hand_made_cube_with_exact_zeros():
     o, d = [c[0] for c in rr.CUBE_RAYS], [c[1] for c in rr.CUBE_RAYS]
     ref = rr.first_hit(o, d, rr.CUBE_V, rr.CUBE_T)
