@@ -171,7 +171,8 @@ def vertex_colors(model, vertices, normals, chunk=1 << 20, autocast=True):
 
 
 def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, min_points=0, largest_only=False,
-                    normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
+                    normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, clean=False,
+                    min_shell_triangles=0, largest_shell_only=False):
     """extract_geometry with what a viewer needs next to the geometry, as a dict: vertices, triangles, normals (extract_mesh's
     with_normals) and colors (vertex_colors), None where not asked for; field (the density volume, filtered where min_points > 0
     or largest_only), threshold, and counts = (components found, components kept, points kept), None where nothing was filtered.
@@ -180,7 +181,11 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
     extraction box; the dict then also holds vertex_map and full_counts = (vertices, triangles) before the simplification.
     smooth=N > 0: N iterations of smooth_mesh (weights smooth_lambda, smooth_mu) over the extraction box, after the colours -- which
     are evaluated at the unsmoothed vertices, on the level set -- and before the simplification; the normals asked for are then
-    face_vertex_normals of the smoothed mesh, and the dict also holds smoothed = N.  smooth=0: the dict is what it was."""
+    face_vertex_normals of the smoothed mesh, and the dict also holds smoothed = N.  smooth=0: the dict is what it was.
+    clean=True: the mesh, with the normals and colours it has by then, goes through clean_mesh (min_shell_triangles,
+    largest_shell_only) last, after the simplification; the dict then also holds topology = dict(before, after), triangle_map, and
+    vertex_map -- clean_mesh's, composed with simplify_mesh's where both ran, so that it still maps the extracted vertices.
+    clean=False: the dict is what it was."""
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -209,6 +214,15 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
     if int(simplify) > 0:
         small = simplify_mesh(vertices, triangles, int(simplify), bmin=lo, bmax=hi, normals=out["normals"], colors=col)
         out.update(small, full_counts=(int(vertices.shape[0]), int(triangles.shape[0])))
+    if clean:
+        first = out.get("vertex_map")
+        done = clean_mesh(out["vertices"], out["triangles"], normals=out["normals"], colors=out["colors"],
+                          min_shell_triangles=min_shell_triangles, largest_shell_only=largest_shell_only)
+        vmap = done["vertex_map"]
+        if first is not None:  # extracted vertex -> simplified vertex -> cleaned vertex
+            vmap = torch.where(first >= 0, vmap[first.clamp(min=0).long()], torch.full_like(first, -1))
+        out.update(vertices=done["vertices"], triangles=done["triangles"], normals=done["normals"], colors=done["colors"],
+                   vertex_map=vmap, triangle_map=done["triangle_map"], topology=dict(before=done["before"], after=done["after"]))
     return out
 
 
@@ -395,7 +409,7 @@ def simplify_mesh(vertices, triangles, grid, bmin=None, bmax=None, normals=None,
     cell means, normals renormalised ((0,0,0) where the mean is zero or not finite), colours clamped to [0,1] --, and vertex_map [V]
     int32, the new index of every input vertex (-1: not finite, or in a cell no surviving triangle touches).  Every sum is an integer
     sum: the result is bit-identical from run to run (include/pvd_hip_mesh_simplify.h; csrc/mesh_simplify.hip).  Duplicate output
-    triangles are not merged and the result is not guaranteed manifold.  No vertex that keeps an index moves further than one cell
+    triangles are not merged and the result is not guaranteed manifold: clean_mesh cancels the collapsed sheets those duplicates are.  No vertex that keeps an index moves further than one cell
     (plus rounding) per axis.  One read-back: the two totals."""
     import pvd_hip
     dev = vertices.device
@@ -458,6 +472,83 @@ def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, bmin=None
     out = torch.empty_like(vertices)
     pvd_hip.mesh_smooth_run(vertices, T, lo, hi, ws, float(lam), float(mu), int(iterations), out)
     return (out, totals) if return_totals else out
+
+
+def _topology_dict(totals):
+    import pvd_hip
+    d = {k: int(x) for k, x in zip(pvd_hip.MESH_TOPO_TOTALS, totals)}
+    d["euler"] = d["referenced"] - d["edges"] + d["survivors"]
+    d["closed"] = d["unbalanced"] == 0
+    d["manifold"] = not (d["boundary"] or d["inconsistent"] or d["non_manifold"] or d["duplicate"] or d["cancelled"])
+    return d
+
+
+def _topo_build(vertices, triangles, with_flags):
+    """(vertices, triangles as the kernels take them, workspace, totals [16] int64 on the device, tri_flags, vertex_shell)."""
+    import pvd_hip
+    dev = vertices.device
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    ws = torch.empty(pvd_hip.mesh_topo_workspace_bytes(V, T), dtype=torch.uint8, device=dev)
+    totals = torch.empty(16, dtype=torch.int64, device=dev)
+    flags = torch.empty(T, dtype=torch.uint8, device=dev) if with_flags else None
+    shell = torch.empty(V, dtype=torch.int32, device=dev) if with_flags else None
+    pvd_hip.mesh_topo_build(vertices, triangles, ws, totals, flags, shell)
+    return vertices, triangles, ws, totals, flags, shell
+
+
+def mesh_topology(vertices, triangles, return_flags=False):
+    """Whether the mesh is a valid surface, as a dict of Python ints (include/pvd_hip_mesh_topo.h; csrc/mesh_topo.hip): valid and
+    invalid triangles (an index outside [0, V), a corner that is not finite, a repeated index); duplicate and cancelled ones (the
+    valid triangles on one vertex set keep one survivor in the orientation of their majority, or none when the two orientations
+    balance); survivors; referenced (vertices a survivor uses); edges of the survivors and how many of them are boundary (one
+    triangle), inconsistent (two triangles that traverse it in the same direction), non_manifold (three or more) and unbalanced
+    (traversed forwards and backwards a different number of times); shells (connected sets of survivors), largest_size and
+    largest_label (the smallest vertex index of the largest shell, -1 without one).  Then euler = referenced - edges + survivors,
+    closed (unbalanced == 0) and manifold (no boundary, inconsistent, non-manifold edge, no duplicate, no cancelled triangle).
+    return_flags=True adds the device tensors tri_flags [T] uint8 (bit0 invalid, bit1 duplicate, bit2 cancelled, bit3 / bit4 / bit5: a
+    survivor with a boundary / inconsistent / non-manifold edge) and vertex_shell [V] int32 (the shell's label, -1: not referenced).
+    Every figure is an integer that does not depend on any order: bit-identical from run to run.  One read-back: the totals."""
+    _, _, _, totals, flags, shell = _topo_build(vertices, triangles, return_flags)
+    out = _topology_dict(totals.tolist())
+    if return_flags:
+        out.update(tri_flags=flags, vertex_shell=shell)
+    return out
+
+
+def clean_mesh(vertices, triangles, normals=None, colors=None, min_shell_triangles=0, largest_shell_only=False):
+    """The mesh without what makes it an invalid surface, as a dict of device tensors: triangles [T',3] int32 -- the survivors of
+    mesh_topology (invalid and duplicate triangles dropped, collapsed sheets cancelled: the duplicates simplify_mesh leaves are
+    exactly those) whose shell has at least min_shell_triangles survivors and, with largest_shell_only, is the largest one, in input
+    order and corner order --, vertices [V',3] f32 -- the vertices those triangles use, in input order, bits copied --, normals and
+    colors (None where not given) gathered by the same selection, vertex_map [V] and triangle_map [T] int32 (the new index, -1:
+    dropped), and before / after, the mesh_topology dicts of the input and of the result.  Nothing is re-oriented, no hole is filled,
+    no vertex is split or merged.  Cleaning twice changes nothing.  Two read-backs (before's totals, the two counts); after comes
+    from a second build on the result, which costs what mesh_topology costs on it, one more read-back included."""
+    import pvd_hip
+    dev = vertices.device
+    vertices, triangles, ws, totals, _, _ = _topo_build(vertices, triangles, False)
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    before = _topology_dict(totals.tolist())
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    pvd_hip.mesh_topo_clean_count(V, T, ws, int(min_shell_triangles), bool(largest_shell_only), counts)
+    Vn, Tn = (int(x) for x in counts.tolist())
+    out_v = torch.empty(Vn, 3, dtype=torch.float32, device=dev)
+    out_t = torch.empty(Tn, 3, dtype=torch.int32, device=dev)
+    vmap = torch.empty(V, dtype=torch.int32, device=dev)
+    tmap = torch.empty(T, dtype=torch.int32, device=dev)
+    pvd_hip.mesh_topo_clean_emit(vertices, triangles, ws, out_v, out_t, vmap, tmap)
+    slot = torch.where(vmap >= 0, vmap, torch.full_like(vmap, Vn)).long()  # the dropped vertices all go to one row behind the end
+
+    def gathered(a):  # by vertex_map, without the read-back a boolean mask would make
+        if a is None:
+            return None
+        a = a.reshape(V, -1)
+        return torch.empty(Vn + 1, a.shape[1], dtype=a.dtype, device=dev).index_copy_(0, slot, a)[:Vn].contiguous()
+    nrm, col = gathered(normals), gathered(colors)
+    return dict(vertices=out_v, triangles=out_t, normals=nrm, colors=col, vertex_map=vmap, triangle_map=tmap, before=before,
+                after=mesh_topology(out_v, out_t))
 
 
 def face_vertex_normals(vertices, triangles):

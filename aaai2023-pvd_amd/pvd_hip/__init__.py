@@ -111,12 +111,14 @@ ENTRY_POINTS_MESH_SIMPLIFY = ("pvd_mesh_simplify_workspace_bytes", "pvd_mesh_sim
 ENTRY_POINTS_MESH_RAY = ("pvd_mesh_ray_workspace_bytes", "pvd_mesh_ray_count", "pvd_mesh_ray_build", "pvd_mesh_ray_cast")
 # ... and the Taubin smoothing of include/pvd_hip_mesh_smooth.h (tests/test_abi_mesh_smooth.py)
 ENTRY_POINTS_MESH_SMOOTH = ("pvd_mesh_smooth_workspace_bytes", "pvd_mesh_smooth_build", "pvd_mesh_smooth_run")
+# ... and the topology report and clean-up of include/pvd_hip_mesh_topo.h (tests/test_abi_mesh_topo.py)
+ENTRY_POINTS_MESH_TOPO = ("pvd_mesh_topo_workspace_bytes", "pvd_mesh_topo_build", "pvd_mesh_topo_clean_count", "pvd_mesh_topo_clean_emit")
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
-              + ENTRY_POINTS_MESH_SMOOTH):
+              + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -132,6 +134,7 @@ _lib.pvd_mesh_dist_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_simplify_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_ray_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_smooth_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_topo_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -1979,3 +1982,80 @@ def mesh_smooth_run(vertices, T, bmin, bmax, workspace, lam, mu, iterations, out
         raise PvdHipError("iterations must be 0 .. %d, got %d" % (MESH_SMOOTH_MAX_ITERATIONS, iterations))
     _call("pvd_mesh_smooth_run", dev, _p(vertices), _u32(V), _u32(T), _p(bmin), _p(bmax), _p(workspace), ctypes.c_size_t(workspace.numel()),
           ctypes.c_double(lam), ctypes.c_double(mu), _u32(iterations), _p(out_vertices))
+
+
+# --------------------------------------------------------------------------- topology report and clean-up (include/pvd_hip_mesh_topo.h)
+MESH_TOPO_TOTALS = ("valid", "invalid", "duplicate", "cancelled", "survivors", "referenced", "edges", "boundary", "inconsistent",
+                    "non_manifold", "unbalanced", "shells", "largest_size", "largest_label")  # entries 0 .. 13 of the 16 totals
+
+
+def mesh_topo_workspace_bytes(V, T):
+    """pvd_mesh_topo_workspace_bytes: bytes of workspace mesh_topo_build / _clean_count / _clean_emit need for V vertices and T
+    triangles."""
+    ok = all(0 <= int(x) < 2 ** 32 for x in (V, T))
+    n = int(_lib.pvd_mesh_topo_workspace_bytes(_u32(V), _u32(T))) if ok else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_topo_workspace_bytes: V and T must be below 2^31, got V=%d T=%d" % (int(V), int(T)))
+    return n
+
+
+def _mesh_topo_mesh(vertices, triangles):
+    _f32_all(vertices=vertices)
+    _want(triangles, torch.int32, "triangles")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    return int(vertices.shape[0]), int(triangles.shape[0])
+
+
+def mesh_topo_build(vertices, triangles, workspace, totals, tri_flags=None, vertex_shell=None):
+    """pvd_mesh_topo_build: the topology of the mesh (vertices [V,3] f32, triangles [T,3] int32) into the workspace (uint8,
+    mesh_topo_workspace_bytes(V, T)); totals int64 [16] on the device (MESH_TOPO_TOTALS names the first 14); tri_flags [T] uint8 and
+    vertex_shell [V] int32 where given."""
+    dev = _dev(vertices, triangles, workspace, totals, tri_flags, vertex_shell)
+    V, T = _mesh_topo_mesh(vertices, triangles)
+    _mesh_workspace(workspace, mesh_topo_workspace_bytes(V, T), "mesh_topo_workspace_bytes(V, T)")
+    _want(totals, torch.int64, "totals")
+    if totals.numel() < 16:
+        raise PvdHipError("totals must hold 16 int64 values")
+    if tri_flags is not None:
+        _want(tri_flags, torch.uint8, "tri_flags")
+        if tri_flags.numel() != T:
+            raise PvdHipError("tri_flags must hold T bytes")
+    if vertex_shell is not None:
+        _want(vertex_shell, torch.int32, "vertex_shell")
+        if vertex_shell.numel() != V:
+            raise PvdHipError("vertex_shell must hold V int32 values")
+    _call("pvd_mesh_topo_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(workspace), ctypes.c_size_t(workspace.numel()),
+          _p(totals), _p(tri_flags), _p(vertex_shell))
+
+
+def mesh_topo_clean_count(V, T, workspace, min_shell_triangles, largest_only, counts):
+    """pvd_mesh_topo_clean_count: counts int64 [2] on the device <- (kept vertices, kept triangles) for the filter, from the workspace
+    mesh_topo_build left for the same V and T."""
+    dev = _dev(workspace, counts)
+    V, T, min_shell_triangles = int(V), int(T), int(min_shell_triangles)
+    _mesh_workspace(workspace, mesh_topo_workspace_bytes(V, T), "mesh_topo_workspace_bytes(V, T)")
+    _want(counts, torch.int64, "counts")
+    if counts.numel() < 2:
+        raise PvdHipError("counts must hold 2 int64 values")
+    if not 0 <= min_shell_triangles < 2 ** 32:
+        raise PvdHipError("min_shell_triangles must be 0 .. 2^32 - 1, got %d" % min_shell_triangles)
+    _call("pvd_mesh_topo_clean_count", dev, _u32(V), _u32(T), _p(workspace), ctypes.c_size_t(workspace.numel()), _u32(min_shell_triangles),
+          _u32(1 if largest_only else 0), _p(counts))
+
+
+def mesh_topo_clean_emit(vertices, triangles, workspace, out_vertices, out_triangles, vertex_map, triangle_map):
+    """pvd_mesh_topo_clean_emit: out_vertices [V',3] f32, out_triangles [T',3] int32, vertex_map [V] int32 and triangle_map [T] int32
+    for the SAME mesh and the workspace the last mesh_topo_clean_count left."""
+    dev = _dev(vertices, triangles, workspace, out_vertices, out_triangles, vertex_map, triangle_map)
+    V, T = _mesh_topo_mesh(vertices, triangles)
+    _mesh_workspace(workspace, mesh_topo_workspace_bytes(V, T), "mesh_topo_workspace_bytes(V, T)")
+    _f32_all(out_vertices=out_vertices)
+    for name, a, n in (("out_triangles", out_triangles, None), ("vertex_map", vertex_map, V), ("triangle_map", triangle_map, T)):
+        _want(a, torch.int32, name)
+        if n is not None and a.numel() != n:
+            raise PvdHipError("%s must hold %d int32 values" % (name, n))
+    if out_vertices.dim() != 2 or out_vertices.shape[1] != 3 or out_triangles.dim() != 2 or out_triangles.shape[1] != 3:
+        raise PvdHipError("out_vertices must be [V',3] and out_triangles [T',3]")
+    _call("pvd_mesh_topo_clean_emit", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(workspace), ctypes.c_size_t(workspace.numel()),
+          _p(out_vertices), _p(out_triangles), _p(vertex_map), _p(triangle_map))

@@ -6,6 +6,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
   python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
                               [--min-component N] [--largest-only] [--normals] [--colors] [--simplify G [--simplify-report]]
                               [--smooth N [--smooth-lambda L --smooth-mu M] [--smooth-report]] [--render-check N]
+                              [--clean [--min-shell N] [--largest-shell-only]] [--topology-report]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
 The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
@@ -28,8 +29,13 @@ absolute difference of the two depths over the pixels where both hit.  Both dept
 mesh's is the ray cast's t (unit directions); the model's render returns its composited depth normalised to the ray's interval in
 the inference box, clamp(depth - near, 0) / (far - near), and is brought back with near + depth * (far - near), near and far from the
 model's own slab test (aabb_infer, min_near).  The composited depth is the weight-summed sample distance, not divided by the
-opacity, so it falls short of the surface where the model is not opaque."""
+opacity, so it falls short of the surface where the model is not opaque.
+--clean runs clean_mesh (pvd/mesh.py, csrc/mesh_topo.hip) last, on the mesh about to be written: invalid and duplicate triangles go,
+collapsed sheets -- the duplicates --simplify leaves -- cancel, --min-shell N drops the shells of fewer than N triangles and
+--largest-shell-only all but the largest one.  --topology-report prints one JSON line of mesh_topology for the mesh about to be
+written (triangle, edge and shell counts, euler, closed, manifold); with --clean two lines, before and after the clean-up."""
 import argparse
+import json
 import os
 import sys
 
@@ -40,7 +46,8 @@ sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
 
 from pvd.checkpoint import load_student_checkpoint  # noqa: E402
 from pvd.config import PVDConfig  # noqa: E402
-from pvd.mesh import compare_meshes, default_threshold, extract_mesh, extract_surface, render_mesh, smooth_mesh, write_ply  # noqa: E402
+from pvd.mesh import (compare_meshes, default_threshold, extract_mesh, extract_surface, mesh_topology, render_mesh, smooth_mesh,  # noqa: E402
+                      write_ply)
 from pvd.ops import hip_ops  # noqa: E402
 from pvd.workload import make_model  # noqa: E402
 
@@ -103,7 +110,13 @@ def main():
     ap.add_argument("--smooth-report", action="store_true", help="measure the smoothed mesh against the unsmoothed one")
     ap.add_argument("--render-check", type=int, default=0, metavar="N",
                     help="render the coloured mesh and the model from N views and print PSNR, SSIM and the depth difference (needs --colors)")
+    ap.add_argument("--clean", action="store_true", help="drop invalid and duplicate triangles and cancel collapsed sheets before writing")
+    ap.add_argument("--min-shell", type=int, default=0, metavar="N", help="with --clean: drop the shells of fewer than N triangles")
+    ap.add_argument("--largest-shell-only", action="store_true", help="with --clean: keep the largest shell only")
+    ap.add_argument("--topology-report", action="store_true", help="print mesh_topology of the mesh about to be written as JSON")
     a = ap.parse_args()
+    if (a.min_shell > 0 or a.largest_shell_only) and not a.clean:
+        ap.error("--min-shell and --largest-shell-only need --clean")
     if a.render_check > 0 and not a.colors:
         ap.error("--render-check needs --colors")
     dev = torch.device("cuda:0")
@@ -117,7 +130,7 @@ def main():
     filtering = a.min_component > 0 or a.largest_only
     m = extract_surface(model, resolution=a.resolution, threshold=thresh, min_points=a.min_component, largest_only=a.largest_only,
                         normals=a.normals, colors=a.colors, simplify=a.simplify, smooth=a.smooth, smooth_lambda=a.smooth_lambda,
-                        smooth_mu=a.smooth_mu)
+                        smooth_mu=a.smooth_mu, clean=a.clean, min_shell_triangles=a.min_shell, largest_shell_only=a.largest_shell_only)
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
     write_ply(out, m["vertices"], m["triangles"], normals=m["normals"], colors=m["colors"])
     carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
@@ -145,6 +158,14 @@ def main():
             diagonal = float((aabb[3:] - aabb[:3]).double().norm()) / a.simplify
             d = compare_meshes(full_v, full_t, m["vertices"], m["triangles"], tau=diagonal)
             print("simplified against original: hausdorff %.6g, chamfer %.6g, cell diagonal %.6g" % (d["hausdorff"], d["chamfer"], diagonal))
+    if a.clean:
+        before, after = m["topology"]["before"], m["topology"]["after"]
+        print("clean: %d -> %d triangles (%d invalid, %d duplicate, %d cancelled), %d -> %d shells"
+              % (before["valid"] + before["invalid"], after["survivors"], before["invalid"], before["duplicate"], before["cancelled"],
+                 before["shells"], after["shells"]))
+    if a.topology_report:
+        for top in ((m["topology"]["before"], m["topology"]["after"]) if a.clean else (mesh_topology(m["vertices"], m["triangles"]),)):
+            print(json.dumps(top))
     if a.render_check > 0:
         rep, depth_diff, n = render_check(model, m, a.render_check)
         print("render check, %d views at 200 x 200, mesh against the model's volume render: PSNR %.2f dB, SSIM %.4f, mean |depth difference| "
