@@ -364,7 +364,7 @@ def sample_surface(vertices, triangles, n, seed):
     return (w[:, :, None] * corners[pick]).sum(dim=1).to(torch.float32)
 
 
-def compare_meshes(va, ta, vb, tb, tau, max_dist=None, samples=0, seed=0):
+def compare_meshes(va, ta, vb, tb, tau, max_dist=None, samples=0, seed=0, volume=0):
     """How far apart two meshes are, as a dict.  The points of a mesh are its vertices, or `samples` surface samples
     (sample_surface; seeds `seed` for A and `seed + 1` for B) when samples > 0; every point of A is measured against mesh B and
     the other way round (mesh_distance; max_dist defaults to the diagonal of the joint bounding box).
@@ -375,7 +375,13 @@ def compare_meshes(va, ta, vb, tb, tau, max_dist=None, samples=0, seed=0):
         n_a, n_b         points measured;  saturated_a, saturated_b: those with no triangle within max_dist (or not finite)
     Saturated rows count as max_dist in the means and the maxima and never as within tau; rows that are not finite are left out
     of the means, the maxima and the shares' denominators.  The
-    reductions run in float64 on the device and come back in one read-back (the default max_dist costs one more)."""
+    reductions run in float64 on the device and come back in one read-back (the default max_dist costs one more).
+    volume=R > 0 adds a volume overlap: both meshes are voxelised (voxelize_mesh) on one R^3 lattice over the joint bounding box, and
+        iou                  points inside both / points inside either (0.0 where neither has any)
+        volume_a, volume_b   points inside x the volume of a lattice cell
+        leaky_a, leaky_b     columns of the lattice that saw the mesh open or inconsistently oriented (voxelize_mesh); not 0: the
+                             mesh has no inside there, and the three figures above mean little
+    join the dict."""
     dev = va.device
     va, vb = va.to(torch.float32).reshape(-1, 3), vb.to(torch.float32).reshape(-1, 3)
     if max_dist is None:
@@ -396,9 +402,12 @@ def compare_meshes(va, ta, vb, tb, tau, max_dist=None, samples=0, seed=0):
                             (tri < 0).sum().to(torch.float64)])
     both = torch.cat([one_side(pa, vb, tb), one_side(pb, va, ta)]).tolist()
     (m_ab, h_ab, prec, sat_a), (m_ba, h_ba, rec, sat_b) = both[:4], both[4:]
-    return dict(a_to_b=m_ab, b_to_a=m_ba, chamfer=m_ab + m_ba, hausdorff=max(h_ab, h_ba), precision=prec, recall=rec,
-                fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0, n_a=int(pa.shape[0]), n_b=int(pb.shape[0]),
-                saturated_a=int(sat_a), saturated_b=int(sat_b))
+    out = dict(a_to_b=m_ab, b_to_a=m_ba, chamfer=m_ab + m_ba, hausdorff=max(h_ab, h_ba), precision=prec, recall=rec,
+               fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0, n_a=int(pa.shape[0]), n_b=int(pb.shape[0]),
+               saturated_a=int(sat_a), saturated_b=int(sat_b))
+    if int(volume) > 0:
+        out.update(_volume_overlap(va, ta, vb, tb, volume))
+    return out
 
 
 def simplify_mesh(vertices, triangles, grid, bmin=None, bmax=None, normals=None, colors=None):
@@ -686,3 +695,127 @@ def evaluate_mesh_views(vertices, triangles, colors, poses, intrinsics, H, W, tr
     if keep_images:
         report["images"] = images
     return report
+
+
+# ------------------------------------------------------------------------------------------------ inside and outside: winding numbers
+def _winding_mesh(vertices, triangles, bmin, bmax, grid):
+    """The two-dimensional grid of include/pvd_hip_mesh_winding.h over the mesh: (T, G, pairs, workspace).  One read-back: the two
+    totals of the count pass."""
+    import pvd_hip
+    dev = vertices.device
+    T = int(triangles.shape[0])
+    G = default_grid(T) if grid is None else int(grid)  # (a grid outside 1 .. 1024 is an error of the binding's, not clamped)
+    lo, hi = _finite_box(vertices) if bmin is None or bmax is None else (None, None)
+    if bmin is not None:
+        lo = torch.as_tensor(bmin, dtype=torch.float32, device=dev).reshape(3).contiguous()
+    if bmax is not None:
+        hi = torch.as_tensor(bmax, dtype=torch.float32, device=dev).reshape(3).contiguous()
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    pvd_hip.mesh_winding_count(vertices, triangles, lo, hi, G, totals)
+    pairs = int(totals.tolist()[0])
+    ws = torch.empty(pvd_hip.mesh_winding_workspace_bytes(T, G, pairs), dtype=torch.uint8, device=dev)
+    pvd_hip.mesh_winding_build(vertices, triangles, lo, hi, G, pairs, ws)
+    return T, G, pairs, ws
+
+
+def mesh_winding(points, vertices, triangles, bmin=None, bmax=None, grid=None):
+    """w [N] int32 on the device: the winding number of every row of points [N,3] about the mesh (vertices [V,3] f32, triangles [T,3]
+    int32) -- the signed crossings of the ray along +z, in unfused float64 with a tie rule that counts a ray through a shared edge or
+    vertex once (include/pvd_hip_mesh_winding.h; csrc/mesh_winding.hip).  +1 inside a closed mesh with outward normals (extract_mesh's
+    orientation), 0 outside; pvd_hip.MESH_WINDING_INVALID for a row that is not finite.  Triangles with an index outside [0, V) or a
+    corner that is not finite are ignored.  The grid of grid^2 cells (default: default_grid(T); 1 .. 1024, anything else raises) lies
+    over the x / y extent of bmin .. bmax (default: the bounding box of the finite vertices); neither changes a bit of the result."""
+    import pvd_hip
+    points = points.to(torch.float32).reshape(-1, 3).contiguous()
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    T, G, pairs, ws = _winding_mesh(vertices, triangles, bmin, bmax, grid)
+    w = torch.empty(points.shape[0], dtype=torch.int32, device=vertices.device)
+    pvd_hip.mesh_winding_points(points, T, G, pairs, ws, w)
+    return w
+
+
+def mesh_contains(points, vertices, triangles, bmin=None, bmax=None, grid=None):
+    """bool [N] on the device: mesh_winding(...) != 0; False for a row that is not finite."""
+    import pvd_hip
+    w = mesh_winding(points, vertices, triangles, bmin, bmax, grid)
+    return (w != 0) & (w != pvd_hip.MESH_WINDING_INVALID)
+
+
+def voxelize_mesh(vertices, triangles, R, bmin, bmax, grid=None, return_totals=False):
+    """w [R,R,R] int32 on the device, x-major as density_field fills its volume: the winding number of the mesh at every point of the
+    R^3 lattice of the box bmin .. bmax (R: 2 .. 1024), bit for bit what mesh_winding returns for those points, a column of R points
+    per ray.  (w != 0).float() is a field that extract_mesh(., 0.5, bmin, bmax), label_components and drop_components accept.
+    return_totals=True: (w, dict) with `inside` (points with w != 0), `positive` (w > 0), `leaky_columns` (columns of the lattice
+    whose crossings do not sum to 0: not 0 for a mesh that is open, or inconsistently oriented, above that column) and `max_abs`."""
+    import pvd_hip
+    dev = vertices.device
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    R = int(R)
+    lo, hi = _box(bmin, bmax, dev)
+    T, G, pairs, ws = _winding_mesh(vertices, triangles, None, None, grid)
+    w = torch.empty(R, R, R, dtype=torch.int32, device=dev) if 2 <= R <= pvd_hip.MESH_WINDING_MAX_R else torch.empty(0, dtype=torch.int32, device=dev)
+    totals = torch.zeros(4, dtype=torch.int64, device=dev)
+    pvd_hip.mesh_winding_lattice(R, lo, hi, T, G, pairs, ws, w, totals)
+    if not return_totals:
+        return w
+    return w, dict(zip(pvd_hip.MESH_WINDING_TOTALS, (int(x) for x in totals.tolist())))
+
+
+def mesh_signed_distance(points, vertices, triangles, max_dist, bmin=None, bmax=None, grid=None):
+    """(sdf [N] f32, tri [N] int32), device tensors: mesh_distance's distance and triangle, the distance with a sign -- positive inside
+    the mesh (mesh_contains), negative outside: the project's convention that inside is the larger value.  The magnitude and tri are
+    mesh_distance's bits: a row saturated at max_dist stays at max_dist, with its sign, and a row that is not finite stays NaN."""
+    dist, tri = mesh_distance(points, vertices, triangles, max_dist, bmin, bmax, grid)
+    inside = mesh_contains(points, vertices, triangles, bmin, bmax, grid)
+    return torch.where(inside, dist, -dist), tri
+
+
+@torch.no_grad()
+def mesh_to_sdf(vertices, triangles, R, bmin, bmax, max_dist, chunk=1 << 21):
+    """sdf [R,R,R] f32 on the device: the signed distance (positive inside, saturated at +-max_dist) from every point of the R^3
+    lattice of the box bmin .. bmax to the mesh -- the sign from voxelize_mesh, the magnitude from the point-to-mesh distance at
+    lattice points made on the device `chunk` at a time (the float32 lattice of include/pvd_hip_mesh_winding.h).
+    extract_mesh(mesh_to_sdf(...), 0.0, bmin, bmax) is a remesh at another resolution."""
+    import pvd_hip
+    dev = vertices.device
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    R = int(R)
+    w = voxelize_mesh(vertices, triangles, R, bmin, bmax)
+    lo, hi = _box(bmin, bmax, dev)
+    # a tensor divisor: a true float32 division (a Python scalar divisor is turned into a multiplication by its rounded reciprocal)
+    steps = torch.arange(R, dtype=torch.float32, device=dev)[:, None] / torch.full((1, 1), float(R - 1), dtype=torch.float32, device=dev)
+    axes = steps * (hi - lo)[None, :] + lo[None, :]  # [R,3]
+    T = int(triangles.shape[0])
+    G = default_grid(T)
+    box_lo, box_hi = _finite_box(vertices)
+    ws = torch.empty(pvd_hip.mesh_dist_workspace_bytes(T, G), dtype=torch.uint8, device=dev)
+    pvd_hip.mesh_dist_build(vertices, triangles, box_lo, box_hi, G, ws)
+    sdf = torch.empty(R, R, R, dtype=torch.float32, device=dev)
+    flat, N = sdf.view(-1), R ** 3
+    for s in range(0, N, int(chunk)):
+        n = torch.arange(s, min(s + int(chunk), N), dtype=torch.int64, device=dev)
+        pts = torch.stack([axes[n // (R * R), 0], axes[(n // R) % R, 1], axes[n % R, 2]], dim=1).contiguous()
+        tri = torch.empty(n.numel(), dtype=torch.int32, device=dev)
+        pvd_hip.mesh_dist_query(pts, T, G, ws, float(max_dist), flat[s:s + n.numel()], tri)
+    inside = (w != 0) & (w != pvd_hip.MESH_WINDING_INVALID)
+    return torch.where(inside, sdf, -sdf)
+
+
+def _volume_overlap(va, ta, vb, tb, R):
+    """compare_meshes(volume=R): both meshes voxelised on one R^3 lattice over the joint bounding box of their finite vertices."""
+    R = int(R)
+    lo_a, hi_a = _finite_box(va)
+    lo_b, hi_b = _finite_box(vb)
+    lo, hi = torch.minimum(lo_a, lo_b), torch.maximum(hi_a, hi_b)
+    wa, tot_a = voxelize_mesh(va, ta, R, lo, hi, return_totals=True)
+    wb, tot_b = voxelize_mesh(vb, tb, R, lo, hi, return_totals=True)
+    in_a, in_b = wa != 0, wb != 0
+    both, either = (int(x) for x in torch.stack([(in_a & in_b).sum(), (in_a | in_b).sum()]).tolist())
+    cell = 1.0
+    for l, h in zip(lo.tolist(), hi.tolist()):
+        cell *= (h - l) / (R - 1)  # the lattice spacing of the axis
+    return dict(iou=both / either if either else 0.0, volume_a=tot_a["inside"] * cell, volume_b=tot_b["inside"] * cell,
+                leaky_a=tot_a["leaky_columns"], leaky_b=tot_b["leaky_columns"])

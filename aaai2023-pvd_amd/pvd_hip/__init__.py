@@ -113,12 +113,15 @@ ENTRY_POINTS_MESH_RAY = ("pvd_mesh_ray_workspace_bytes", "pvd_mesh_ray_count", "
 ENTRY_POINTS_MESH_SMOOTH = ("pvd_mesh_smooth_workspace_bytes", "pvd_mesh_smooth_build", "pvd_mesh_smooth_run")
 # ... and the topology report and clean-up of include/pvd_hip_mesh_topo.h (tests/test_abi_mesh_topo.py)
 ENTRY_POINTS_MESH_TOPO = ("pvd_mesh_topo_workspace_bytes", "pvd_mesh_topo_build", "pvd_mesh_topo_clean_count", "pvd_mesh_topo_clean_emit")
+# ... and the winding numbers of include/pvd_hip_mesh_winding.h (tests/test_abi_mesh_winding.py)
+ENTRY_POINTS_MESH_WINDING = ("pvd_mesh_winding_workspace_bytes", "pvd_mesh_winding_count", "pvd_mesh_winding_build", "pvd_mesh_winding_points",
+                             "pvd_mesh_winding_lattice")
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
-              + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO):
+              + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -135,6 +138,7 @@ _lib.pvd_mesh_simplify_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_ray_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_smooth_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_topo_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_winding_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -1924,6 +1928,88 @@ def mesh_ray_cast(origins, dirs, T, G, pairs, workspace, t_min, t_max, t, tri, b
     _mesh_workspace(workspace, mesh_ray_workspace_bytes(T, G, pairs), "mesh_ray_workspace_bytes(T, G, pairs)")
     _call("pvd_mesh_ray_cast", dev, _p(origins), _p(dirs), _u32(N), _u32(T), _u32(G), _u64(pairs), _p(workspace),
           ctypes.c_size_t(workspace.numel()), _f32(t_min), _f32(t_max), _p(t), _p(tri), _p(bary))
+
+
+# --------------------------------------------------------------------------- winding numbers (include/pvd_hip_mesh_winding.h)
+MESH_WINDING_MAX_G = 1024  # PVD_MESH_WINDING_MAX_G: cells per axis of the two-dimensional grid, 1 .. 1024
+MESH_WINDING_MAX_R = 1024  # PVD_MESH_WINDING_MAX_R: points per axis of a lattice, 2 .. 1024
+MESH_WINDING_INVALID = -2 ** 31  # PVD_MESH_WINDING_INVALID: the value of a point that is not finite
+MESH_WINDING_TOTALS = ("inside", "positive", "leaky_columns", "max_abs")  # the four totals of mesh_winding_lattice
+
+
+def mesh_winding_workspace_bytes(T, G, pairs):
+    """pvd_mesh_winding_workspace_bytes: bytes of workspace mesh_winding_build and the two queries need for T triangles, G^2 cells and
+    `pairs` (cell, triangle) pairs (the first total of mesh_winding_count)."""
+    ok = 0 <= int(T) < 2 ** 32 and 0 <= int(G) < 2 ** 32 and 0 <= int(pairs) < 2 ** 64
+    n = int(_lib.pvd_mesh_winding_workspace_bytes(_u32(T), _u32(G), _u64(pairs))) if ok else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_winding_workspace_bytes: G must be 1 .. %d, T and pairs below 2^31, got T=%d G=%d pairs=%d"
+                          % (MESH_WINDING_MAX_G, int(T), int(G), int(pairs)))
+    return n
+
+
+def _mesh_winding_mesh(vertices, triangles, bmin, bmax, G):
+    V, T = _mesh_and_box(vertices, triangles, bmin, bmax)
+    if not 1 <= int(G) <= MESH_WINDING_MAX_G:
+        raise PvdHipError("G must be 1 .. %d, got %d" % (MESH_WINDING_MAX_G, int(G)))
+    return V, T
+
+
+def mesh_winding_count(vertices, triangles, bmin, bmax, G, totals):
+    """pvd_mesh_winding_count: totals int64 [2] on the device <- (the (cell, triangle) pairs, the outside triangles) of the mesh
+    (vertices [V,3] f32, triangles [T,3] int32) over G^2 cells of the x / y extent of the box bmin .. bmax (device f32 [3] each)."""
+    dev = _dev(vertices, triangles, bmin, bmax, totals)
+    V, T = _mesh_winding_mesh(vertices, triangles, bmin, bmax, G)
+    _want(totals, torch.int64, "totals")
+    if totals.numel() < 2:
+        raise PvdHipError("totals must hold 2 int64 values")
+    _call("pvd_mesh_winding_count", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _p(totals))
+
+
+def mesh_winding_build(vertices, triangles, bmin, bmax, G, pairs, workspace):
+    """pvd_mesh_winding_build: bins the valid triangles of the SAME mesh, box and G as mesh_winding_count, with the `pairs` it left, and
+    leaves in the workspace (uint8, mesh_winding_workspace_bytes(T, G, pairs)) what mesh_winding_points / _lattice need."""
+    dev = _dev(vertices, triangles, bmin, bmax, workspace)
+    V, T = _mesh_winding_mesh(vertices, triangles, bmin, bmax, G)
+    _mesh_workspace(workspace, mesh_winding_workspace_bytes(T, G, pairs), "mesh_winding_workspace_bytes(T, G, pairs)")
+    _call("pvd_mesh_winding_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _u64(pairs),
+          _p(workspace), ctypes.c_size_t(workspace.numel()))
+
+
+def mesh_winding_points(points, T, G, pairs, workspace, winding):
+    """pvd_mesh_winding_points: winding [N] int32 <- the winding number of every row of points [N,3] f32 against the mesh
+    mesh_winding_build left in the workspace for the SAME T, G and pairs; MESH_WINDING_INVALID for a row that is not finite."""
+    dev = _dev(points, workspace, winding)
+    _f32_all(points=points)
+    _want(winding, torch.int32, "winding")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise PvdHipError("points must be [N,3]")
+    N = int(points.shape[0])
+    if winding.numel() != N:
+        raise PvdHipError("winding must hold N values")
+    _mesh_workspace(workspace, mesh_winding_workspace_bytes(T, G, pairs), "mesh_winding_workspace_bytes(T, G, pairs)")
+    _call("pvd_mesh_winding_points", dev, _p(points), _u32(N), _u32(T), _u32(G), _u64(pairs), _p(workspace), ctypes.c_size_t(workspace.numel()),
+          _p(winding))
+
+
+def mesh_winding_lattice(R, lat_bmin, lat_bmax, T, G, pairs, workspace, winding, totals):
+    """pvd_mesh_winding_lattice: winding [R,R,R] int32 (x-major, z fastest) <- the winding number of every point of the R^3 lattice over
+    lat_bmin .. lat_bmax (device f32 [3] each) against the mesh mesh_winding_build left in the workspace for the SAME T, G and pairs;
+    totals int64 [4] on the device <- MESH_WINDING_TOTALS."""
+    dev = _dev(lat_bmin, lat_bmax, workspace, winding, totals)
+    _f32_all(lat_bmin=lat_bmin, lat_bmax=lat_bmax)
+    _want(winding, torch.int32, "winding")
+    _want(totals, torch.int64, "totals")
+    R = int(R)
+    if not 2 <= R <= MESH_WINDING_MAX_R:
+        raise PvdHipError("R must be 2 .. %d, got %d" % (MESH_WINDING_MAX_R, R))
+    if lat_bmin.numel() < 3 or lat_bmax.numel() < 3:
+        raise PvdHipError("lat_bmin / lat_bmax must hold 3 floats")
+    if winding.numel() != R ** 3 or totals.numel() < 4:
+        raise PvdHipError("winding must hold R^3 values and totals 4")
+    _mesh_workspace(workspace, mesh_winding_workspace_bytes(T, G, pairs), "mesh_winding_workspace_bytes(T, G, pairs)")
+    _call("pvd_mesh_winding_lattice", dev, _u32(R), _p(lat_bmin), _p(lat_bmax), _u32(T), _u32(G), _u64(pairs), _p(workspace),
+          ctypes.c_size_t(workspace.numel()), _p(winding), _p(totals))
 
 
 # --------------------------------------------------------------------------- Taubin smoothing (include/pvd_hip_mesh_smooth.h)
