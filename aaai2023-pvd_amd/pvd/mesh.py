@@ -172,7 +172,7 @@ def vertex_colors(model, vertices, normals, chunk=1 << 20, autocast=True):
 
 def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, min_points=0, largest_only=False,
                     normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, clean=False,
-                    min_shell_triangles=0, largest_shell_only=False):
+                    min_shell_triangles=0, largest_shell_only=False, texture=0):
     """extract_geometry with what a viewer needs next to the geometry, as a dict: vertices, triangles, normals (extract_mesh's
     with_normals) and colors (vertex_colors), None where not asked for; field (the density volume, filtered where min_points > 0
     or largest_only), threshold, and counts = (components found, components kept, points kept), None where nothing was filtered.
@@ -185,7 +185,11 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
     clean=True: the mesh, with the normals and colours it has by then, goes through clean_mesh (min_shell_triangles,
     largest_shell_only) last, after the simplification; the dict then also holds topology = dict(before, after), triangle_map, and
     vertex_map -- clean_mesh's, composed with simplify_mesh's where both ran, so that it still maps the extracted vertices.
-    clean=False: the dict is what it was."""
+    clean=False: the dict is what it was.
+    texture=S > 0: an atlas with S x S texels per pair of triangles is baked last (bake_texture: the model's colour head at the surface
+    point of every texel, seen along the mesh's normals, or the face normals where none were asked for), on the final mesh -- after
+    the smoothing, the simplification and the clean-up; the dict then also holds texture [Ht,Wt,3], uv [T,3,2] and texture_cell = S.
+    texture=0: the dict is what it was."""
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -223,6 +227,9 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
             vmap = torch.where(first >= 0, vmap[first.clamp(min=0).long()], torch.full_like(first, -1))
         out.update(vertices=done["vertices"], triangles=done["triangles"], normals=done["normals"], colors=done["colors"],
                    vertex_map=vmap, triangle_map=done["triangle_map"], topology=dict(before=done["before"], after=done["after"]))
+    if int(texture) > 0:
+        baked = bake_texture(model, out["vertices"], out["triangles"], int(texture), normals=out["normals"])
+        out.update(texture=baked["texture"], uv=baked["uv"], texture_cell=int(texture))
     return out
 
 
@@ -618,7 +625,8 @@ def mesh_raycast(origins, dirs, vertices, triangles, t_min=0.0, t_max=float("inf
     return t, tri, bary
 
 
-def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, colors=None, bg_color=1.0, grid=None):
+def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, colors=None, bg_color=1.0, grid=None, texture=None,
+                texture_cell=None):
     """The mesh seen from the camera `pose` ([4,4] cam2world; rays from pvd.scene.get_rays, unit directions, so t is a distance), as
     a dict of device tensors:
         depth [H,W] f32     the distance to the first hit, 0 where nothing is hit
@@ -626,7 +634,9 @@ def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, color
         normal [H,W,3]      the barycentric mean of the vertex normals [V,3], renormalised, where they are given; otherwise the unit
                             face normal turned towards the camera; (0,0,0) off the mesh (and where the mean or the face is null)
         color [H,W,3]       the barycentric mean of the vertex colours [V,3] over bg_color (a float or 3 floats); None without colors
-    The interpolation is plain torch gathers on the cast's output."""
+    The interpolation is plain torch gathers on the cast's output.
+    texture [Ht,Wt,3] with texture_cell = S (bake_texture's, for these triangles): color is sample_texture's bilinear lookup of the
+    atlas at the hits instead (csrc/mesh_tex.hip), whatever colors holds."""
     from .scene import get_rays
     dev = vertices.device
     pose = torch.as_tensor(pose, dtype=torch.float32, device=dev).reshape(4, 4)
@@ -636,7 +646,7 @@ def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, color
     mask = tri >= 0
     if int(triangles.shape[0]) == 0 or int(vertices.shape[0]) == 0:  # nothing to gather from: every pixel is background
         col = None
-        if colors is not None:
+        if colors is not None or texture is not None:
             col = torch.as_tensor(bg_color, dtype=torch.float32, device=dev).expand(H, W, 3).contiguous()
         return dict(depth=torch.zeros(H, W, dtype=torch.float32, device=dev), mask=mask.reshape(H, W), tri=tri.reshape(H, W),
                     bary=bary.reshape(H, W, 2), normal=torch.zeros(H, W, 3, dtype=torch.float32, device=dev), color=col)
@@ -662,23 +672,32 @@ def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, color
     if colors is not None:
         bg = torch.as_tensor(bg_color, dtype=torch.float32, device=dev).expand(3)
         col = torch.where(mask[:, None], mix(colors), bg[None, :]).reshape(H, W, 3)
+    if texture is not None:
+        if texture_cell is None:
+            raise ValueError("texture needs texture_cell, the cell edge S it was baked with")
+        col = sample_texture(texture, texture_cell, int(triangles.shape[0]), tri, bary, bg_color=bg_color).reshape(H, W, 3)
     return dict(depth=torch.where(mask, t, torch.zeros_like(t)).reshape(H, W), mask=mask.reshape(H, W), tri=tri.reshape(H, W),
                 bary=bary.reshape(H, W, 2), normal=nrm.reshape(H, W, 3), color=col)
 
 
 @torch.no_grad()
-def evaluate_mesh_views(vertices, triangles, colors, poses, intrinsics, H, W, truth, bg_color=1.0, grid=None, keep_images=False):
+def evaluate_mesh_views(vertices, triangles, colors, poses, intrinsics, H, W, truth, bg_color=1.0, grid=None, keep_images=False,
+                        texture=None, texture_cell=None):
     """Render the coloured mesh from poses [P,4,4] (render_mesh) and measure each view's colour image against `truth` the way
     pvd.metrics.evaluate_views does for a model: a tensor [P,H,W,3], or a callable (rays_o, rays_d) -> [H*W,3].  Returns
     ImageMeter.report() plus "coverage", the share of all pixels that hit the mesh (and, with keep_images, the views under
-    "images")."""
+    "images").  texture, texture_cell: render_mesh's -- the views are coloured from the atlas, and colors may be None."""
     from .metrics import ImageMeter
     from .scene import get_rays
     meter = ImageMeter()
     images, hit, pixels = [], None, 0
     for v, pose in enumerate(poses):
         pose = torch.as_tensor(pose, dtype=torch.float32, device=vertices.device).reshape(4, 4)
-        out = render_mesh(vertices, triangles, pose, intrinsics, H, W, colors=colors, bg_color=bg_color, grid=grid)
+        if texture is None:
+            out = render_mesh(vertices, triangles, pose, intrinsics, H, W, colors=colors, bg_color=bg_color, grid=grid)
+        else:
+            out = render_mesh(vertices, triangles, pose, intrinsics, H, W, colors=colors, bg_color=bg_color, grid=grid, texture=texture,
+                              texture_cell=texture_cell)
         if callable(truth):
             r = get_rays(pose[None], intrinsics, int(H), int(W), -1)
             gt = truth(r["rays_o"], r["rays_d"])
@@ -819,3 +838,236 @@ def _volume_overlap(va, ta, vb, tb, R):
         cell *= (h - l) / (R - 1)  # the lattice spacing of the axis
     return dict(iou=both / either if either else 0.0, volume_a=tot_a["inside"] * cell, volume_b=tot_b["inside"] * cell,
                 leaky_a=tot_a["leaky_columns"], leaky_b=tot_b["leaky_columns"])
+
+
+# ------------------------------------------------------------------------------------------------ texture atlases
+def texture_layout(T, S):
+    """dict(cells_per_row, rows, width, height, cell, triangles) of the per-triangle atlas of include/pvd_hip_mesh_tex.h: two triangles
+    share a square cell of S x S texels (S 4 .. 64), C cells per row with C the smallest integer whose square holds ceil(T / 2) cells.
+    A side above 16384 texels raises."""
+    import pvd_hip
+    C, rows, Wt, Ht = pvd_hip.mesh_tex_layout(int(T), int(S))
+    return dict(cells_per_row=C, rows=rows, width=Wt, height=Ht, cell=int(S), triangles=int(T))
+
+
+def texture_uv(T, S, device=None):
+    """[T,3,2] f32: the texture coordinates of the three corners of every triangle in the OBJ convention (u to the right, v up, the
+    image's first row at v = 1): the centres of the texels that hold the corners' baked values.  The header's closed form, in torch."""
+    lay = texture_layout(T, S)
+    C, Wt, Ht, S, m = lay["cells_per_row"], lay["width"], lay["height"], int(S), int(S) - 3
+    f = torch.arange(int(T), dtype=torch.int64, device=device)
+    k, odd = f // 2, (f % 2) == 1
+    ax = (k % C) * S + torch.where(odd, S - 1, 0)
+    ay = (k // C) * S + torch.where(odd, S - 1, 0)
+    step = torch.where(odd, -m, m)
+    X = torch.stack([ax, ax + step, ax], dim=1).to(torch.float64) + 0.5
+    Y = torch.stack([ay, ay, ay + step], dim=1).to(torch.float64) + 0.5
+    return torch.stack([X / Wt, 1.0 - Y / Ht], dim=2).to(torch.float32)
+
+
+def texture_points(vertices, triangles, S, normals=None, rows=None):
+    """(x, n) [(row1 - row0) * width, 3] f32 on the device: the surface point and the normal of every texel of the image rows
+    rows = (row0, row1) (default: the whole atlas) of the mesh's atlas (csrc/mesh_tex.hip).  n: the weights of x on the vertex normals
+    [V,3], left unnormalised, or the face normal without them.  Six NaNs for a texel nothing owns and for the texels of a triangle with an
+    index outside [0, V) or a corner (or given normal) that is not finite."""
+    import pvd_hip
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    if normals is not None:
+        normals = normals.to(torch.float32).reshape(-1, 3).contiguous()
+    lay = texture_layout(int(triangles.shape[0]), S)
+    row0, row1 = (0, lay["height"]) if rows is None else (int(rows[0]), int(rows[1]))
+    count = max(row1 - row0, 0) * lay["width"]
+    x = torch.empty(count, 3, dtype=torch.float32, device=vertices.device)
+    n = torch.empty(count, 3, dtype=torch.float32, device=vertices.device)
+    pvd_hip.mesh_tex_points(vertices, triangles, normals, int(S), row0, row1, x, n)
+    return x, n
+
+
+def _unit_rows(n):
+    length = torch.linalg.norm(n, dim=1, keepdim=True)
+    ok = torch.isfinite(length) & (length > 0)
+    return torch.where(ok, n / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(n))
+
+
+@torch.no_grad()
+def bake_texture(source, vertices, triangles, S, normals=None, chunk=1 << 20):
+    """dict(texture [Ht,Wt,3] f32 in [0,1], uv [T,3,2] f32, layout): the colour of `source` at the surface point of every texel of the
+    mesh's atlas (texture_layout, texture_points).  source: a model -- vertex_colors(model, x, n / |n|), the colour head seen straight
+    on, as the vertex colours are taken -- or a callable (x [M,3], n_unit [M,3]) -> [M,3].  Baked in bands of whole image rows of about
+    `chunk` texels; texels nothing owns, and those of invalid triangles, get the colour 0 and never reach the source."""
+    T = int(triangles.reshape(-1, 3).shape[0])
+    lay = texture_layout(T, S)
+    Wt, Ht = lay["width"], lay["height"]
+    texture = torch.empty(Ht, Wt, 3, dtype=torch.float32, device=vertices.device)
+    band = max(1, int(chunk) // Wt)
+    is_model = hasattr(source, "aabb_infer")
+    for row0 in range(0, Ht, band):
+        row1 = min(row0 + band, Ht)
+        x, n = texture_points(vertices, triangles, S, normals=normals, rows=(row0, row1))
+        if is_model:  # rows that are not finite come back as colour 0
+            rgb = vertex_colors(source, x, _unit_rows(n), chunk=chunk)
+        else:
+            good = torch.isfinite(x).all(dim=1) & torch.isfinite(n).all(dim=1)
+            rgb = torch.zeros_like(x)
+            if bool(good.any()):
+                rgb[good] = source(x[good].contiguous(), _unit_rows(n[good]).contiguous()).to(torch.float32).reshape(-1, 3).clamp(0.0, 1.0)
+        texture[row0:row1] = rgb.reshape(row1 - row0, Wt, 3)
+    return dict(texture=texture, uv=texture_uv(T, S, device=vertices.device), layout=lay)
+
+
+def sample_texture(texture, S, T, tri, bary, bg_color=1.0):
+    """[..., 3] f32 on the device: the bilinear lookup of texture [Ht,Wt,3] (the atlas of T triangles at the cell edge S) at the hits
+    (tri [...] int32, bary [..., 2] f32) of mesh_raycast; bg_color (a float or 3 floats) where tri is -1.  Reads the hit triangle's own
+    cell only (include/pvd_hip_mesh_tex.h; csrc/mesh_tex.hip)."""
+    import pvd_hip
+    dev = texture.device
+    texture = texture.to(torch.float32).contiguous()
+    shape = tuple(tri.shape)
+    tri = tri.to(torch.int32).reshape(-1).contiguous()
+    bary = bary.to(torch.float32).reshape(-1, 2).contiguous()
+    bg = torch.as_tensor(bg_color, dtype=torch.float32, device=dev).expand(3).contiguous()
+    color = torch.empty(int(tri.shape[0]), 3, dtype=torch.float32, device=dev)
+    pvd_hip.mesh_tex_sample(texture, int(T), int(S), tri, bary, bg, color)
+    return color.reshape(shape + (3,))
+
+
+def _png_chunk(kind, data):
+    import struct
+    import zlib
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xffffffff)
+
+
+def write_png(path, image):
+    """8-bit RGB PNG of image [H,W,3] (floats in [0,1]: round(clamp(c, 0, 1) * 255), NaN as 0; or uint8), first row on top: stdlib zlib,
+    filter 0 on every row, one IDAT chunk."""
+    import struct
+    import zlib
+
+    import numpy as np
+    a = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("image must be [H,W,3] with H, W >= 1")
+    if a.dtype != np.uint8:
+        with np.errstate(invalid="ignore"):
+            a = np.rint(np.clip(np.nan_to_num(a.astype(np.float32), nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+    H, W = a.shape[:2]
+    rows = np.zeros((H, 1 + 3 * W), np.uint8)  # the filter byte 0, then the row
+    rows[:, 1:] = a.reshape(H, 3 * W)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(_png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)))
+        f.write(_png_chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)))
+        f.write(_png_chunk(b"IEND", b""))
+    return path
+
+
+def read_png(path):
+    """[H,W,3] f32 in [0,1] (byte / 255), a host tensor, of a file write_png wrote: 8-bit RGB, not interlaced, filter 0 on every row (any
+    number of IDAT chunks); anything else raises."""
+    import struct
+    import zlib
+
+    import numpy as np
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("%s: not a PNG" % path)
+    pos, head, body = 8, None, b""
+    while pos + 12 <= len(data):
+        n, kind = struct.unpack(">I", data[pos:pos + 4])[0], data[pos + 4:pos + 8]
+        chunk = data[pos + 8:pos + 8 + n]
+        if len(chunk) != n or struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0] != (zlib.crc32(kind + chunk) & 0xffffffff):
+            raise ValueError("%s: a damaged chunk" % path)
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", chunk)
+        elif kind == b"IDAT":
+            body += chunk
+        elif kind == b"IEND":
+            break
+        pos += 12 + n
+    if head is None or head[2:] != (8, 2, 0, 0, 0):
+        raise ValueError("%s: not an 8-bit RGB PNG without interlace" % path)
+    W, H = head[:2]
+    rows = np.frombuffer(zlib.decompress(body), np.uint8)
+    if rows.size != H * (1 + 3 * W):
+        raise ValueError("%s: truncated" % path)
+    rows = rows.reshape(H, 1 + 3 * W)
+    if np.any(rows[:, 0] != 0):
+        raise ValueError("%s: a row filter other than 0" % path)
+    return torch.from_numpy(rows[:, 1:].reshape(H, W, 3).astype(np.float32) / np.float32(255.0))
+
+
+def write_obj(path, vertices, triangles, uv, texture_file, normals=None):
+    """Wavefront OBJ with a texture: `v` per vertex, `vn` per vertex where normals [V,3] are given, three `vt` per triangle (uv [T,3,2],
+    texture_uv's), `f a/t` or `f a/t/n` (1-based), and next to it an .mtl of the same name with one material whose map_Kd is
+    texture_file (a name relative to the OBJ).  Floats are written with 9 significant digits: float32 comes back bit for bit."""
+    import os
+
+    import numpy as np
+
+    def host(a, dtype, cols):
+        return np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=dtype).reshape(-1, cols)
+    v, t, w = host(vertices, np.float32, 3), host(triangles, np.int64, 3), host(uv, np.float32, 2)
+    if len(w) != 3 * len(t):
+        raise ValueError("uv must be [T,3,2]")
+    mtl = os.path.splitext(path)[0] + ".mtl"
+    lines = ["mtllib %s" % os.path.basename(mtl), "usemtl material0"]
+    lines += ["v %.9g %.9g %.9g" % tuple(r) for r in v.tolist()]
+    if normals is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(r) for r in host(normals, np.float32, 3).tolist()]
+    lines += ["vt %.9g %.9g" % tuple(r) for r in w.tolist()]
+    for f, (a, b, c) in enumerate(t.tolist()):
+        k = 3 * f + 1
+        if normals is not None:
+            lines.append("f %d/%d/%d %d/%d/%d %d/%d/%d" % (a + 1, k, a + 1, b + 1, k + 1, b + 1, c + 1, k + 2, c + 1))
+        else:
+            lines.append("f %d/%d %d/%d %d/%d" % (a + 1, k, b + 1, k + 1, c + 1, k + 2))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    with open(mtl, "w") as f:
+        f.write("newmtl material0\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s\n" % texture_file)
+    return path
+
+
+def read_obj(path):
+    """dict(vertices [V,3] f32, triangles [T,3] int32, uv [T,3,2] f32, normals [V,3] f32 | None, mtllib, texture_file) of a file
+    write_obj wrote, as host tensors: `v`, `vn`, `vt`, triangular `f a/t` or `f a/t/n` with the normal's index equal to the vertex's,
+    `mtllib`, `usemtl`; texture_file is the map_Kd of the .mtl next to the file (None where there is none).  Anything else raises."""
+    import os
+
+    import numpy as np
+    v, vn, vt, fv, ft, mtllib = [], [], [], [], [], None
+    with open(path) as f:
+        for line in f:
+            words = line.split()
+            if not words or words[0].startswith("#") or words[0] == "usemtl":
+                continue
+            if words[0] == "v" and len(words) == 4:
+                v.append([float(x) for x in words[1:]])
+            elif words[0] == "vn" and len(words) == 4:
+                vn.append([float(x) for x in words[1:]])
+            elif words[0] == "vt" and len(words) == 3:
+                vt.append([float(x) for x in words[1:]])
+            elif words[0] == "f" and len(words) == 4:
+                parts = [w.split("/") for w in words[1:]]
+                if any(len(p) not in (2, 3) or (len(p) == 3 and p[2] != p[0]) for p in parts):
+                    raise ValueError("%s: unexpected face %r" % (path, line))
+                fv.append([int(p[0]) - 1 for p in parts])
+                ft.append([int(p[1]) - 1 for p in parts])
+            elif words[0] == "mtllib" and len(words) == 2:
+                mtllib = words[1]
+            else:
+                raise ValueError("%s: unexpected line %r" % (path, line))
+    texture_file = None
+    if mtllib is not None and os.path.exists(os.path.join(os.path.dirname(path), mtllib)):
+        with open(os.path.join(os.path.dirname(path), mtllib)) as f:
+            for line in f:
+                if line.startswith("map_Kd "):
+                    texture_file = line[len("map_Kd "):].strip()
+    vt = np.array(vt, np.float32).reshape(-1, 2)
+    ft = np.array(ft, np.int64).reshape(-1, 3)
+    return dict(vertices=torch.from_numpy(np.array(v, np.float32).reshape(-1, 3)),
+                triangles=torch.from_numpy(np.array(fv, np.int32).reshape(-1, 3)), uv=torch.from_numpy(vt[ft].reshape(-1, 3, 2)),
+                normals=torch.from_numpy(np.array(vn, np.float32).reshape(-1, 3)) if vn else None, mtllib=mtllib,
+                texture_file=texture_file)

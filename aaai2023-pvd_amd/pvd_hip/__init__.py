@@ -116,12 +116,14 @@ ENTRY_POINTS_MESH_TOPO = ("pvd_mesh_topo_workspace_bytes", "pvd_mesh_topo_build"
 # ... and the winding numbers of include/pvd_hip_mesh_winding.h (tests/test_abi_mesh_winding.py)
 ENTRY_POINTS_MESH_WINDING = ("pvd_mesh_winding_workspace_bytes", "pvd_mesh_winding_count", "pvd_mesh_winding_build", "pvd_mesh_winding_points",
                              "pvd_mesh_winding_lattice")
+# ... and the texture atlas of include/pvd_hip_mesh_tex.h (tests/test_abi_mesh_tex.py)
+ENTRY_POINTS_MESH_TEX = ("pvd_mesh_tex_layout", "pvd_mesh_tex_points", "pvd_mesh_tex_sample")
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
-              + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING):
+              + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING + ENTRY_POINTS_MESH_TEX):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -2010,6 +2012,62 @@ def mesh_winding_lattice(R, lat_bmin, lat_bmax, T, G, pairs, workspace, winding,
     _mesh_workspace(workspace, mesh_winding_workspace_bytes(T, G, pairs), "mesh_winding_workspace_bytes(T, G, pairs)")
     _call("pvd_mesh_winding_lattice", dev, _u32(R), _p(lat_bmin), _p(lat_bmax), _u32(T), _u32(G), _u64(pairs), _p(workspace),
           ctypes.c_size_t(workspace.numel()), _p(winding), _p(totals))
+
+
+# --------------------------------------------------------------------------- texture atlas (include/pvd_hip_mesh_tex.h)
+MESH_TEX_MIN_S = 4  # PVD_MESH_TEX_MIN_S: the smallest cell edge in texels
+MESH_TEX_MAX_S = 64  # PVD_MESH_TEX_MAX_S: the largest
+MESH_TEX_MAX_SIDE = 16384  # PVD_MESH_TEX_MAX_SIDE: the largest width or height of an atlas
+
+
+def mesh_tex_layout(T, S):
+    """pvd_mesh_tex_layout: (C, rows, Wt, Ht) of the atlas of T triangles at the cell edge S (host only)."""
+    out = (ctypes.c_uint32 * 4)()
+    ok = 0 <= int(T) < 2 ** 32 and 0 <= int(S) < 2 ** 32
+    status = _lib.pvd_mesh_tex_layout(_u32(T), _u32(S), out) if ok else -2
+    if status != 0:
+        raise PvdHipError("pvd_mesh_tex_layout: S must be %d .. %d and no side of the atlas above %d, got T=%d S=%d"
+                          % (MESH_TEX_MIN_S, MESH_TEX_MAX_S, MESH_TEX_MAX_SIDE, int(T), int(S)))
+    return tuple(int(v) for v in out)
+
+
+def mesh_tex_points(vertices, triangles, normals, S, row0, row1, x, n):
+    """pvd_mesh_tex_points: x, n [(row1 - row0) * Wt, 3] f32 <- the surface point and the normal of every texel of the image rows
+    row0 .. row1 - 1 of the atlas of the mesh (vertices [V,3] f32, triangles [T,3] int32; normals [V,3] f32 or None: face normals); six
+    NaNs for a texel nothing owns or whose triangle is invalid."""
+    dev = _dev(vertices, triangles, normals, x, n)
+    _f32_all(vertices=vertices, x=x, n=n)
+    _want(triangles, torch.int32, "triangles")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    if normals is not None:
+        _f32_all(normals=normals)
+        if normals.dim() != 2 or tuple(normals.shape) != (V, 3):
+            raise PvdHipError("normals must be [V,3]")
+    Wt, Ht = mesh_tex_layout(T, S)[2:]
+    row0, row1 = int(row0), int(row1)
+    if not 0 <= row0 <= row1 <= Ht:
+        raise PvdHipError("rows must satisfy 0 <= row0 <= row1 <= %d, got %d, %d" % (Ht, row0, row1))
+    if x.numel() != (row1 - row0) * Wt * 3 or n.numel() != x.numel():
+        raise PvdHipError("x and n must hold (row1 - row0) * Wt * 3 values")
+    _call("pvd_mesh_tex_points", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(normals), _u32(S), _u32(row0), _u32(row1),
+          _p(x), _p(n))
+
+
+def mesh_tex_sample(texture, T, S, tri, bary, bg3, color):
+    """pvd_mesh_tex_sample: color [N,3] f32 <- the bilinear lookup of texture [Ht,Wt,3] f32 (the atlas of T triangles at the cell edge S)
+    at tri [N] int32, bary [N,2] f32 (mesh_ray_cast's); bg3 (device f32 [3]) where tri is outside 0 .. T - 1."""
+    dev = _dev(texture, tri, bary, bg3, color)
+    _f32_all(texture=texture, bary=bary, bg3=bg3, color=color)
+    _want(tri, torch.int32, "tri")
+    Wt, Ht = mesh_tex_layout(T, S)[2:]
+    if tuple(texture.shape) != (Ht, Wt, 3):
+        raise PvdHipError("texture must be [%d,%d,3] for T=%d S=%d, got %s" % (Ht, Wt, int(T), int(S), tuple(texture.shape)))
+    N = int(tri.numel())
+    if bary.numel() != 2 * N or color.numel() != 3 * N or bg3.numel() < 3:
+        raise PvdHipError("bary must hold 2 N, color 3 N and bg3 3 values")
+    _call("pvd_mesh_tex_sample", dev, _p(texture), _u32(T), _u32(S), _p(tri), _p(bary), _u32(N), _p(bg3), _p(color))
 
 
 # --------------------------------------------------------------------------- Taubin smoothing (include/pvd_hip_mesh_smooth.h)

@@ -6,7 +6,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
   python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
                               [--min-component N] [--largest-only] [--normals] [--colors] [--simplify G [--simplify-report]]
                               [--smooth N [--smooth-lambda L --smooth-mu M] [--smooth-report]] [--render-check N]
-                              [--clean [--min-shell N] [--largest-shell-only]] [--topology-report]
+                              [--clean [--min-shell N] [--largest-shell-only]] [--topology-report] [--texture S]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
 The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
@@ -33,7 +33,12 @@ opacity, so it falls short of the surface where the model is not opaque.
 --clean runs clean_mesh (pvd/mesh.py, csrc/mesh_topo.hip) last, on the mesh about to be written: invalid and duplicate triangles go,
 collapsed sheets -- the duplicates --simplify leaves -- cancel, --min-shell N drops the shells of fewer than N triangles and
 --largest-shell-only all but the largest one.  --topology-report prints one JSON line of mesh_topology for the mesh about to be
-written (triangle, edge and shell counts, euler, closed, manifold); with --clean two lines, before and after the clean-up."""
+written (triangle, edge and shell counts, euler, closed, manifold); with --clean two lines, before and after the clean-up.
+--texture S bakes a texture atlas for the mesh about to be written (pvd/mesh.py: bake_texture, csrc/mesh_tex.hip: S x S texels per pair of
+triangles, S 4 .. 64, the model's colour at the surface point of every texel) and writes an .obj, an .mtl and a .png next to the PLY.
+With --render-check N it prints the PSNR and SSIM of three renders against the model's own: the textured mesh, the same mesh with its
+vertex colours, and the full-resolution mesh (no --simplify) with its vertex colours -- what the texture wins back of what the
+simplification lost."""
 import argparse
 import json
 import os
@@ -47,14 +52,15 @@ sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
 from pvd.checkpoint import load_student_checkpoint  # noqa: E402
 from pvd.config import PVDConfig  # noqa: E402
 from pvd.mesh import (compare_meshes, default_threshold, extract_mesh, extract_surface, mesh_topology, render_mesh, smooth_mesh,  # noqa: E402
-                      write_ply)
+                      write_obj, write_ply, write_png)
 from pvd.ops import hip_ops  # noqa: E402
 from pvd.workload import make_model  # noqa: E402
 
 
 @torch.no_grad()
-def render_check(model, m, views, res=200):
-    """(ImageMeter report of the mesh's colour image against the model's render, mean |depth difference| over the pixels both hit,
+def render_check(model, m, views, res=200, textured=False):
+    """textured: the mesh is coloured from m["texture"] (render_mesh's texture) instead of m["colors"].
+    (ImageMeter report of the mesh's colour image against the model's render, mean |depth difference| over the pixels both hit,
     their number), over `views` pose_spherical cameras on a circle at the reference's radius and scale.  Depths in world units along
     the ray: the model's normalised depth d is turned back into near + d (far - near) with the near / far of its own slab test."""
     import numpy as np
@@ -66,7 +72,11 @@ def render_check(model, m, views, res=200):
     meter, diff, both = ImageMeter(), torch.zeros((), dtype=torch.float64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
     for q in range(views):
         pose = torch.from_numpy(nerf_matrix_to_ngp(pose_spherical(-180.0 + 360.0 * q / views, -30.0, 4.0)).astype(np.float32)).to(dev)
-        mesh = render_mesh(m["vertices"], m["triangles"], pose, intr, res, res, colors=m["colors"], bg_color=1.0)
+        if textured:
+            mesh = render_mesh(m["vertices"], m["triangles"], pose, intr, res, res, bg_color=1.0, texture=m["texture"],
+                               texture_cell=m["texture_cell"])
+        else:
+            mesh = render_mesh(m["vertices"], m["triangles"], pose, intr, res, res, colors=m["colors"], bg_color=1.0)
         r = get_rays(pose[None], intr, res, res, -1)
         with torch.autocast("cuda", dtype=torch.float16):
             vol = model.render(r["rays_o"], r["rays_d"], staged=True, bg_color=1, perturb=False, max_steps=1024)
@@ -114,11 +124,13 @@ def main():
     ap.add_argument("--min-shell", type=int, default=0, metavar="N", help="with --clean: drop the shells of fewer than N triangles")
     ap.add_argument("--largest-shell-only", action="store_true", help="with --clean: keep the largest shell only")
     ap.add_argument("--topology-report", action="store_true", help="print mesh_topology of the mesh about to be written as JSON")
+    ap.add_argument("--texture", type=int, default=0, metavar="S",
+                    help="bake a texture atlas with S x S texels per pair of triangles (4 .. 64) and write .obj, .mtl and .png next to the PLY")
     a = ap.parse_args()
     if (a.min_shell > 0 or a.largest_shell_only) and not a.clean:
         ap.error("--min-shell and --largest-shell-only need --clean")
-    if a.render_check > 0 and not a.colors:
-        ap.error("--render-check needs --colors")
+    if a.render_check > 0 and not (a.colors or a.texture > 0):
+        ap.error("--render-check needs --colors or --texture")
     dev = torch.device("cuda:0")
     opt = PVDConfig(model_type=a.model_type, resolution0=a.resolution0, plenoxel_res=a.plenoxel_res)
     model = make_model(hip_ops(), opt, a.model_type, False, dev)
@@ -128,11 +140,14 @@ def main():
     model.eval()
     thresh = default_threshold(model) if a.threshold is None else a.threshold
     filtering = a.min_component > 0 or a.largest_only
-    m = extract_surface(model, resolution=a.resolution, threshold=thresh, min_points=a.min_component, largest_only=a.largest_only,
-                        normals=a.normals, colors=a.colors, simplify=a.simplify, smooth=a.smooth, smooth_lambda=a.smooth_lambda,
-                        smooth_mu=a.smooth_mu, clean=a.clean, min_shell_triangles=a.min_shell, largest_shell_only=a.largest_shell_only)
+    kw = dict(resolution=a.resolution, threshold=thresh, min_points=a.min_component, largest_only=a.largest_only, smooth=a.smooth,
+              smooth_lambda=a.smooth_lambda, smooth_mu=a.smooth_mu, clean=a.clean, min_shell_triangles=a.min_shell,
+              largest_shell_only=a.largest_shell_only)
+    compare = a.texture > 0 and a.render_check > 0  # the three renders need the vertex colours too, written or not
+    m = extract_surface(model, normals=a.normals, colors=a.colors or compare, simplify=a.simplify,
+                        **(dict(texture=a.texture) if a.texture > 0 else {}), **kw)
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
-    write_ply(out, m["vertices"], m["triangles"], normals=m["normals"], colors=m["colors"])
+    write_ply(out, m["vertices"], m["triangles"], normals=m["normals"], colors=m["colors"] if a.colors else None)
     carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
     print("%s: %d vertices (%s), %d triangles at density %.6g, resolution %d"
           % (out, m["vertices"].shape[0], carries, m["triangles"].shape[0], thresh, a.resolution))
@@ -166,7 +181,19 @@ def main():
     if a.topology_report:
         for top in ((m["topology"]["before"], m["topology"]["after"]) if a.clean else (mesh_topology(m["vertices"], m["triangles"]),)):
             print(json.dumps(top))
-    if a.render_check > 0:
+    if a.texture > 0:
+        stem = os.path.splitext(out)[0]
+        write_png(stem + ".png", m["texture"])
+        write_obj(stem + ".obj", m["vertices"], m["triangles"], m["uv"], os.path.basename(stem + ".png"), normals=m["normals"])
+        print("%s.obj, .mtl, .png: texture %d x %d, %d x %d texels per pair of triangles"
+              % (stem, m["texture"].shape[1], m["texture"].shape[0], a.texture, a.texture))
+    if compare:
+        full = extract_surface(model, normals=False, colors=True, **kw) if a.simplify > 0 else m
+        for name, mesh, tex in (("textured mesh", m, True), ("vertex-coloured mesh", m, False), ("full-resolution vertex-coloured mesh", full, False)):
+            rep = render_check(model, mesh, a.render_check, textured=tex)[0]
+            print("render check, %d views at 200 x 200, %s (%d triangles) against the model's volume render: PSNR %.2f dB, SSIM %.4f"
+                  % (a.render_check, name, mesh["triangles"].shape[0], rep["psnr"], rep["ssim"]))
+    elif a.render_check > 0:
         rep, depth_diff, n = render_check(model, m, a.render_check)
         print("render check, %d views at 200 x 200, mesh against the model's volume render: PSNR %.2f dB, SSIM %.4f, mean |depth difference| "
               "%.5f (world units along the ray) over %d pixels both hit" % (a.render_check, rep["psnr"], rep["ssim"], depth_diff, n))
