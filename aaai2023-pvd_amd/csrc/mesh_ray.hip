@@ -12,61 +12,14 @@
 // No workgroup waits on another one of the same launch, and no loop retries an atomic.  The order of the pairs inside a cell depends
 // on the run; the cast's (t, index) minimum does not.
 #include "block_scan.h"
-#include "mesh_grid.h"
-
-#include "../../include/pvd_hip_mesh_ray.h"
+#include "mesh_ray_walk.h"
 
 namespace {
 
 using namespace pvd;
+using namespace pvd::mray;  // the workspace's layout, the box, the test and the walk: shared with csrc/mesh_expose.hip
 
-constexpr uint32_t kMaxT = 0x7fffffffu;
-constexpr uint64_t kMaxPairs = 0x7fffffffull;
-
-// header words (uint32): 0 = outside triangles (the list's cursor), 1..3 = bmin, 4..6 = bmax (float bits), 7 = pairs; 64 bytes in all
-constexpr size_t kHeaderBytes = 64;
-
-struct Layout {  // byte offsets into the workspace; the 16-byte records first, so that a 16-byte aligned workspace aligns them
-    size_t packed, start, cursor, bsum, outside, pairs, total;
-};
-
-inline Layout layout(uint32_t T, uint32_t G, uint64_t pairs) {
-    const size_t C = (size_t)G * G * G, NB = (C + kThreads - 1) / kThreads;
-    Layout l;
-    l.packed = kHeaderBytes;
-    l.start = l.packed + 48 * (size_t)T;
-    l.cursor = l.start + 4 * (C + 1);
-    l.bsum = l.cursor + 4 * C;
-    l.outside = l.bsum + 4 * NB;
-    l.pairs = l.outside + 4 * (size_t)T;
-    l.total = l.pairs + 4 * (size_t)pairs;
-    return l;
-}
-
-// the pure parts (box, ranges, the test, the walk) are PVD_HD, __host__ __device__: a CPU build can walk the same code
-PVD_HD float sel3(float x, float y, float z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
-
-struct Box {  // per axis: flat (one layer from -inf to +inf), the bounds, the cell size and its inverse, the dilation eps
-    bool flat[3];
-    double lo[3], hi[3], h[3], inv_h[3], eps[3];
-};
-
-PVD_HD Box box_of(const float *__restrict__ bmin3, const float *__restrict__ bmax3, uint32_t G) {
-    Box b;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double lo = (double)bmin3[a], hi = (double)bmax3[a];
-        const double ext = hi - lo;
-        const bool ok = ext > 0.0 && ext < (double)INFINITY;  // false for NaN
-        b.flat[a] = !ok;
-        b.lo[a] = ok ? lo : 0.0;
-        b.hi[a] = ok ? hi : 0.0;
-        b.h[a] = ok ? ext / (double)G : 0.0;
-        b.inv_h[a] = ok ? (double)G / ext : 0.0;
-        b.eps[a] = ok ? 0x1p-20 * ext : 0.0;
-    }
-    return b;
-}
+static_assert(kCellsPerSum == (size_t)kThreads, "the layout's partial sums are those of k_blocksum");
 
 enum : int { kInvalid = 0, kInside = 1, kOutside = 2 };
 
@@ -163,152 +116,51 @@ __global__ __launch_bounds__(kThreads) void k_mr_fill(const float *__restrict__ 
             }
 }
 
-// ------------------------------------------------------------------------------------------- the watertight test, in float64
-struct Ray {  // the ray's constants, once per lane: the permuted origin, the shear, the permutation
-    double ox, oy, oz, Sx, Sy, Sz;
-    int kx, ky, kz;
-};
-
-PVD_HD Ray ray_of(const double o[3], const double d[3]) {
-    Ray r;
-    const double ax = fabs(d[0]), ay = fabs(d[1]), az = fabs(d[2]);
-    r.kz = ax >= ay && ax >= az ? 0 : (ay >= az ? 1 : 2);  // argmax |d|, ties to the lowest axis
-    r.kx = (r.kz + 1) % 3;
-    r.ky = (r.kx + 1) % 3;
-    const double dz = r.kz == 0 ? d[0] : (r.kz == 1 ? d[1] : d[2]);
-    if (dz < 0.0) {
-        const int s = r.kx;
-        r.kx = r.ky;
-        r.ky = s;
-    }
-    const double dx = r.kx == 0 ? d[0] : (r.kx == 1 ? d[1] : d[2]), dy = r.ky == 0 ? d[0] : (r.ky == 1 ? d[1] : d[2]);
-    r.Sx = dx / dz;
-    r.Sy = dy / dz;
-    r.Sz = 1.0 / dz;
-    r.ox = r.kx == 0 ? o[0] : (r.kx == 1 ? o[1] : o[2]);
-    r.oy = r.ky == 0 ? o[0] : (r.ky == 1 ? o[1] : o[2]);
-    r.oz = r.kz == 0 ? o[0] : (r.kz == 1 ? o[1] : o[2]);
-    return r;
-}
-
+// ------------------------------------------------------------------------------------------------------- the first hit
 struct Best {
     double t;     // the best t so far (starts at t_max)
     int32_t tri;  // its triangle (-1: none yet)
     double v, w;  // V / det, W / det of the best
 };
 
-// record j of the packed array against the ray: include/pvd_hip_mesh_ray.h, steps 3 .. 8 and "Result"
-PVD_HD void test(const float4 *__restrict__ packed, uint32_t j, const Ray &r, double t_min, double t_max, Best &best) {
+struct FirstHit {  // the walk's visitor (csrc/mesh_ray_walk.h): the smallest (t, index) over [t_min, t_max)
+    Ray r;
+    double t_min, t_max;
+    Best best;
+
+    // record j of the packed array against the ray: include/pvd_hip_mesh_ray.h, steps 3 .. 8 and "Result"
+    PVD_HD void test(const float4 *__restrict__ packed, uint32_t j) {
 #pragma clang fp contract(off)
-    const float4 q0 = packed[3 * (size_t)j], q1 = packed[3 * (size_t)j + 1], q2 = packed[3 * (size_t)j + 2];
-    const int32_t idx = (int32_t)f2u(q2.y);
-    if (idx < 0) return;  // an invalid triangle
-    const double Ax = (double)sel3(q0.x, q0.y, q0.z, r.kx) - r.ox, Ay = (double)sel3(q0.x, q0.y, q0.z, r.ky) - r.oy;
-    const double Az = (double)sel3(q0.x, q0.y, q0.z, r.kz) - r.oz;
-    const double Bx = (double)sel3(q0.w, q1.x, q1.y, r.kx) - r.ox, By = (double)sel3(q0.w, q1.x, q1.y, r.ky) - r.oy;
-    const double Bz = (double)sel3(q0.w, q1.x, q1.y, r.kz) - r.oz;
-    const double Cx = (double)sel3(q1.z, q1.w, q2.x, r.kx) - r.ox, Cy = (double)sel3(q1.z, q1.w, q2.x, r.ky) - r.oy;
-    const double Cz = (double)sel3(q1.z, q1.w, q2.x, r.kz) - r.oz;
-    const double Xa = Ax - r.Sx * Az, Ya = Ay - r.Sy * Az;
-    const double Xb = Bx - r.Sx * Bz, Yb = By - r.Sy * Bz;
-    const double Xc = Cx - r.Sx * Cz, Yc = Cy - r.Sy * Cz;
-    const double U = Xc * Yb - Yc * Xb, V = Xa * Yc - Ya * Xc, W = Xb * Ya - Yb * Xa;
-    if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) return;
-    const double det = (U + V) + W;
-    if (det == 0.0) return;
-    const double Za = r.Sz * Az, Zb = r.Sz * Bz, Zc = r.Sz * Cz;
-    const double t = ((U * Za + V * Zb) + W * Zc) / det;
-    if (!(t >= t_min && t < t_max)) return;  // false for NaN
-    if (t < best.t || (t == best.t && best.tri >= 0 && idx < best.tri)) {  // best.t <= t_max throughout
-        best.t = t;
-        best.tri = idx;
-        best.v = V / det;
-        best.w = W / det;
+        const float4 q0 = packed[3 * (size_t)j], q1 = packed[3 * (size_t)j + 1], q2 = packed[3 * (size_t)j + 2];
+        const int32_t idx = (int32_t)f2u(q2.y);
+        if (idx < 0) return;  // an invalid triangle
+        Crossing x;
+        if (!crossing(q0, q1, q2, r, x)) return;
+        if (!(x.t >= t_min && x.t < t_max)) return;  // false for NaN
+        if (x.t < best.t || (x.t == best.t && best.tri >= 0 && idx < best.tri)) {  // best.t <= t_max throughout
+            best.t = x.t;
+            best.tri = idx;
+            best.v = x.V / x.det;
+            best.w = x.W / x.det;
+        }
     }
-}
+    PVD_HD bool found() const { return false; }  // a later triangle may be nearer
+    PVD_HD bool settled(double t_exit) const { return best.tri >= 0 && best.t < t_exit * (1.0 - 0x1p-30); }
+};
 
 // the search of one valid ray
 PVD_HD void cast_ray(const double o[3], const double d[3], uint32_t T, uint32_t G, const uint32_t *__restrict__ header,
                      const uint32_t *__restrict__ start, const uint32_t *__restrict__ list, const uint32_t *__restrict__ outside,
                      const float4 *__restrict__ packed, uint32_t pairs, double t_min, double t_max, Best &best) {
-    const Ray r = ray_of(o, d);
-    const Box box = box_of((const float *)(header + 1), (const float *)(header + 4), G);
-    best.t = t_max;
-    best.tri = -1;
-    best.v = best.w = 0.0;
-    // every index below is clamped: a damaged workspace stays inside itself
-    const uint32_t n_pairs = umin(header[7], pairs), n_out = umin(header[0], T);
-    // (1) clip to the dilated slabs
-    double t0 = t_min, t1 = t_max, inv_d[3];
-    bool touches = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        inv_d[a] = 0.0;
-        if (box.flat[a]) continue;
-        const double e4 = 0.25 * box.eps[a];
-        if (d[a] == 0.0) {
-            if (o[a] < box.lo[a] - e4 || o[a] > box.hi[a] + e4) touches = false;
-            continue;
-        }
-        inv_d[a] = 1.0 / d[a];
-        const double ta = ((box.lo[a] - e4) - o[a]) * inv_d[a], tb = ((box.hi[a] + e4) - o[a]) * inv_d[a];
-        t0 = fmax(t0, fmin(ta, tb));
-        t1 = fmin(t1, fmax(ta, tb));
-    }
-    touches = touches && t0 <= t1;
-    if (touches) {  // far rays: the rounding of a position is no longer small against eps
-        bool far = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (box.flat[a]) continue;
-            double M = fabs(o[a]) + fabs(box.lo[a]) + fabs(box.hi[a]);
-            if (d[a] != 0.0) M += fabs(d[a]) * t1;  // t1 is finite here: this axis has clipped it
-            if (!(0x1p-40 * M <= box.eps[a])) far = true;
-        }
-        if (far) {
-            for (uint32_t j = 0; j < T; ++j) test(packed, j, r, t_min, t_max, best);
-            return;
-        }
-        // (2) the start cell
-        int k[3], step[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            k[a] = box.flat[a] ? 0 : cell_axis(box, a, o[a] + t0 * d[a], G);
-            step[a] = (box.flat[a] || d[a] == 0.0) ? 0 : (d[a] > 0.0 ? 1 : -1);
-        }
-        for (uint32_t it = 0; it < 3u * G; ++it) {  // at most 3 (G - 1) steps
-            // (3) the cell's triangles
-            const uint32_t c = ((uint32_t)k[0] * G + (uint32_t)k[1]) * G + (uint32_t)k[2];
-            const uint32_t s1 = umin(start[c + 1], n_pairs);
-            for (uint32_t s = umin(start[c], n_pairs); s < s1; ++s) {
-                const uint32_t j = list[s];
-                if (j < T) test(packed, j, r, t_min, t_max, best);
-            }
-            // (4) the exit, from the integer face
-            double t_exit = (double)INFINITY;
-            int axis = -1;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                if (step[a] == 0) continue;
-                const double face = box.lo[a] + (double)(k[a] + (step[a] > 0 ? 1 : 0)) * box.h[a];
-                const double te = (face - o[a]) * inv_d[a];
-                if (te < t_exit) {
-                    t_exit = te;
-                    axis = a;
-                }
-            }
-            // (5) stop or step
-            if (axis < 0 || !(t_exit < t1)) break;
-            if (best.tri >= 0 && best.t < t_exit * (1.0 - 0x1p-30)) break;
-            k[axis] += step[axis];
-            if (k[axis] < 0 || k[axis] >= (int)G) break;
-        }
-    }
-    // (6) the outside list
-    for (uint32_t s = 0; s < n_out; ++s) {
-        const uint32_t j = outside[s];
-        if (j < T) test(packed, j, r, t_min, t_max, best);
-    }
+    FirstHit vis;
+    vis.r = ray_of(o, d);
+    vis.t_min = t_min;
+    vis.t_max = t_max;
+    vis.best.t = t_max;
+    vis.best.tri = -1;
+    vis.best.v = vis.best.w = 0.0;
+    walk(o, d, T, G, header, start, list, outside, packed, pairs, t_min, t_max, vis);
+    best = vis.best;
 }
 
 __global__ __launch_bounds__(kThreads) void k_mr_cast(const float *__restrict__ origins, const float *__restrict__ dirs, uint32_t N, uint32_t T,
@@ -336,15 +188,6 @@ __global__ __launch_bounds__(kThreads) void k_mr_cast(const float *__restrict__ 
     out_tri[i] = hit ? best.tri : -1;
     out_bary[2 * (size_t)i] = hit ? (float)best.v : 0.0f;
     out_bary[2 * (size_t)i + 1] = hit ? (float)best.w : 0.0f;
-}
-
-bool in_range(uint32_t T, uint32_t G, uint64_t pairs) { return G >= 1 && G <= PVD_MESH_RAY_MAX_G && T <= kMaxT && pairs <= kMaxPairs; }
-
-int check_args(uint32_t T, uint32_t G, uint64_t pairs, const void *workspace, size_t workspace_bytes) {
-    if (!workspace || ((uintptr_t)workspace & 15u)) return PVD_ERR_INVALID;
-    if (!in_range(T, G, pairs)) return PVD_ERR_UNSUPPORTED;
-    if (workspace_bytes < layout(T, G, pairs).total) return PVD_ERR_INVALID;
-    return PVD_OK;
 }
 
 }  // namespace

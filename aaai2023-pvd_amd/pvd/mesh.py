@@ -590,19 +590,11 @@ def face_vertex_normals(vertices, triangles):
     return torch.where(good, acc / torch.where(good, length, torch.ones_like(length)), torch.zeros_like(acc)).contiguous()
 
 
-def mesh_raycast(origins, dirs, vertices, triangles, t_min=0.0, t_max=float("inf"), bmin=None, bmax=None, grid=None):
-    """(t [N] f32, tri [N] int32, bary [N,2] f32), device tensors: the first hit of every ray (origins [N,3], dirs [N,3]; dirs need not
-    be unit length, t is in units of |dir|) on the mesh (vertices [V,3] f32, triangles [T,3] int32) with t_min <= t < t_max -- the
-    watertight test in unfused float64, rounded once (include/pvd_hip_mesh_ray.h; csrc/mesh_ray.hip).  tri is the triangle, bary the
-    weights of its second and third corner.  (t_max, -1, (0, 0)) where nothing is hit, (NaN, -1, (0, 0)) for a ray that is not finite
-    or has a zero direction.  Triangles with an index outside [0, V) or a corner that is not finite are ignored.  The grid of grid^3
-    cells (default: default_grid(T); 1 .. 256, anything else raises) lies over bmin .. bmax (default: the bounding box of the finite
-    vertices); neither changes a bit of the result, only the time -- but for the edge-on case include/pvd_hip_mesh_ray.h names.  One
-    read-back: the two totals of the count pass."""
+def _ray_grid(vertices, triangles, bmin, bmax, grid):
+    """(T, G, pairs, workspace): the uniform grid of include/pvd_hip_mesh_ray.h over the mesh, as pvd_mesh_ray_cast and pvd_mesh_expose
+    read it.  One read-back: the two totals of the count pass."""
     import pvd_hip
     dev = vertices.device
-    origins = origins.to(torch.float32).reshape(-1, 3).contiguous()
-    dirs = dirs.to(torch.float32).reshape(-1, 3).contiguous()
     vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
     triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
     T = int(triangles.shape[0])
@@ -617,12 +609,128 @@ def mesh_raycast(origins, dirs, vertices, triangles, t_min=0.0, t_max=float("inf
     pairs = int(totals.tolist()[0])
     ws = torch.empty(pvd_hip.mesh_ray_workspace_bytes(T, G, pairs), dtype=torch.uint8, device=dev)
     pvd_hip.mesh_ray_build(vertices, triangles, lo, hi, G, pairs, ws)
+    return T, G, pairs, ws
+
+
+def mesh_raycast(origins, dirs, vertices, triangles, t_min=0.0, t_max=float("inf"), bmin=None, bmax=None, grid=None):
+    """(t [N] f32, tri [N] int32, bary [N,2] f32), device tensors: the first hit of every ray (origins [N,3], dirs [N,3]; dirs need not
+    be unit length, t is in units of |dir|) on the mesh (vertices [V,3] f32, triangles [T,3] int32) with t_min <= t < t_max -- the
+    watertight test in unfused float64, rounded once (include/pvd_hip_mesh_ray.h; csrc/mesh_ray.hip).  tri is the triangle, bary the
+    weights of its second and third corner.  (t_max, -1, (0, 0)) where nothing is hit, (NaN, -1, (0, 0)) for a ray that is not finite
+    or has a zero direction.  Triangles with an index outside [0, V) or a corner that is not finite are ignored.  The grid of grid^3
+    cells (default: default_grid(T); 1 .. 256, anything else raises) lies over bmin .. bmax (default: the bounding box of the finite
+    vertices); neither changes a bit of the result, only the time -- but for the edge-on case include/pvd_hip_mesh_ray.h names.  One
+    read-back: the two totals of the count pass."""
+    import pvd_hip
+    dev = vertices.device
+    origins = origins.to(torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(torch.float32).reshape(-1, 3).contiguous()
+    T, G, pairs, ws = _ray_grid(vertices, triangles, bmin, bmax, grid)
     N = int(origins.shape[0])
     t = torch.empty(N, dtype=torch.float32, device=dev)
     tri = torch.empty(N, dtype=torch.int32, device=dev)
     bary = torch.empty(N, 2, dtype=torch.float32, device=dev)
     pvd_hip.mesh_ray_cast(origins, dirs, T, G, pairs, ws, float(t_min), float(t_max), t, tri, bary)
     return t, tri, bary
+
+
+# ------------------------------------------------------------------------------------------------ exposure: what a view can see
+def exposure_directions(D=64):
+    """[D,3] f32 (a host tensor): the default directions of mesh_exposure, a Fibonacci sphere -- z_i = 1 - (2 i + 1) / D, the azimuth
+    (i + 1/2) pi (3 - sqrt 5), made in float64 and rounded to float32.  The same D gives the same directions; none of the default 64 has
+    a zero component, so none runs along an axis or in a lattice plane of an extracted mesh."""
+    import numpy as np
+    i = np.arange(int(D), dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / float(D)
+    r = np.sqrt(1.0 - z * z)
+    phi = (i + 0.5) * (np.pi * (3.0 - np.sqrt(5.0)))
+    return torch.from_numpy(np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1).astype(np.float32))
+
+
+def mesh_exposure(vertices, triangles, dirs=None, samples=1, bmin=None, bmax=None, grid=None, band=None, return_totals=False):
+    """counts [T,4] int32 on the device: per triangle the front rays cast, the front rays that escaped, the back rays cast and the back rays
+    that escaped -- rays from `samples` points of the triangle (1: the centroid; 4: and three points towards the corners) along every
+    direction of dirs [D,3] (D 1 .. 1024; default exposure_directions(64)); a ray is a front ray where it leaves on the side the
+    triangle's winding faces (the outside of an extract_mesh surface), and it escapes when it meets no other valid triangle: an any-hit
+    walk over mesh_raycast's grid with its watertight test (csrc/pvd_hip_mesh_expose.h has the definition to the operation;
+    csrc/mesh_expose.hip).  A triangle with an index outside [0, V) or a corner that is not finite has four zeros.  Integers: identical
+    from run to run, and independent of grid, the box and band (the triangles per launch; default: all in one) -- but for the edge-on
+    case include/pvd_hip_mesh_ray.h names.  return_totals=True: (counts, dict of rays_cast, rays_escaped, front_exposed, back_exposed and
+    hidden -- valid triangles with a front escape, with a back escape, with none), one more read-back.  See cull_hidden."""
+    import pvd_hip
+    dev = vertices.device
+    T, G, pairs, ws = _ray_grid(vertices, triangles, bmin, bmax, grid)
+    dirs = (exposure_directions(64) if dirs is None else dirs).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    counts = torch.empty(T, 4, dtype=torch.int32, device=dev)
+    totals = torch.zeros(5, dtype=torch.int64, device=dev)
+    step = T if band is None else int(band)
+    if band is not None and step < 1:
+        raise ValueError("band must be at least 1, got %d" % step)
+    for s in range(0, T, max(step, 1)):
+        e = min(s + step, T)
+        pvd_hip.mesh_expose(dirs, int(samples), s, e, T, G, pairs, ws, counts[s:e], totals)
+    if T == 0:  # nothing to launch: the arguments are still checked
+        pvd_hip.mesh_expose(dirs, int(samples), 0, 0, T, G, pairs, ws, counts, totals)
+    if not return_totals:
+        return counts
+    return counts, dict(zip(pvd_hip.MESH_EXPOSE_TOTALS, (int(x) for x in totals.tolist())))
+
+
+def cull_hidden(vertices, triangles, normals=None, colors=None, mode="shells", sides="front", min_escaped=1, dirs=None, samples=1,
+                grid=None, band=None):
+    """The mesh without the geometry no outside view can see, as a dict shaped like clean_mesh's: vertices [V',3] f32 and triangles [T',3]
+    int32 (what is kept, in input order, bits copied), normals and colors (None where not given) by the same selection, vertex_map [V]
+    and triangle_map [T] int32 (the new index, -1: dropped), counts [T,4] (mesh_exposure's, of the input) and report: triangles_before /
+    _after, vertices_before / _after, hidden_triangles (the valid triangles that are not exposed -- in mode="shells" that counts the
+    unexposed triangles of a shell that is kept too, so it is NOT triangles_before - triangles_after there), shells_before, shells_dropped
+    and totals (mesh_exposure's).  A triangle is EXPOSED when at least min_escaped of its front rays escape (sides="front": the orientation is
+    trusted, as extract_mesh gives it) or of its front or of its back rays (sides="either": for meshes of unknown orientation).
+    mode="shells" (default): a shell -- mesh_topology's vertex_shell -- is dropped only when none of its triangles is exposed, so a closed
+    mesh stays closed and mesh_winding, voxelize_mesh and mesh_to_sdf still work on the result: cavity walls and enclosed blobs go, a part
+    that is seen anywhere stays whole.  mode="triangles": every triangle that is not exposed is dropped; THIS OPENS THE SURFACE (the
+    result has boundary edges wherever a visible part continues out of sight).  Triangles with an index outside [0, V) or a corner that is
+    not finite are always dropped; a valid triangle whose first corner has no shell (a cancelled sheet) is judged on its own.  Vertices
+    no kept triangle uses are dropped.  The selection is plain torch (an integer amax scatter per shell, masks, cumulative sums); the
+    rays are the kernel's.  grid and band are mesh_exposure's: band triangles per launch (default: one launch for the whole mesh, several
+    hundred milliseconds for a 256^3 extraction at 64 directions); the box is always the bounding box of the finite vertices."""
+    if mode not in ("shells", "triangles") or sides not in ("front", "either"):
+        raise ValueError("mode must be 'shells' or 'triangles' and sides 'front' or 'either', got %r and %r" % (mode, sides))
+    dev = vertices.device
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    counts, totals = mesh_exposure(vertices, triangles, dirs, samples, grid=grid, band=band, return_totals=True)
+    escaped = counts[:, 1] if sides == "front" else torch.maximum(counts[:, 1], counts[:, 3])
+    exposed = escaped >= max(int(min_escaped), 1)
+    topo = mesh_topology(vertices, triangles, return_flags=True)
+    tl = triangles.long()
+    in_range = ((tl >= 0) & (tl < V)).all(dim=1)
+    safe = torch.where(in_range[:, None], tl, torch.zeros_like(tl))
+    valid = in_range & (torch.isfinite(vertices[safe].reshape(T, 9)).all(dim=1) if V else in_range)
+    label = torch.where(valid, topo["vertex_shell"].long()[safe[:, 0]], torch.full((T,), -1, dtype=torch.int64, device=dev)) if V else \
+        torch.full((T,), -1, dtype=torch.int64, device=dev)
+    slot = torch.where(label >= 0, label, torch.full_like(label, V))  # the triangles without a shell all go to one slot behind the end
+    seen = torch.zeros(V + 1, dtype=torch.int32, device=dev).scatter_reduce_(0, slot, exposed.to(torch.int32), "amax")
+    present = torch.zeros(V + 1, dtype=torch.int32, device=dev).scatter_reduce_(0, slot, valid.to(torch.int32), "amax")
+    if mode == "shells":
+        keep = valid & torch.where(label >= 0, seen[slot] > 0, exposed)
+    else:
+        keep = valid & exposed
+    tmap = torch.where(keep, torch.cumsum(keep.to(torch.int32), 0, dtype=torch.int32) - 1, torch.full((T,), -1, dtype=torch.int32, device=dev))
+    kept = tl[keep]
+    used = torch.zeros(V, dtype=torch.bool, device=dev)
+    used[kept.reshape(-1)] = True
+    vmap = torch.where(used, torch.cumsum(used.to(torch.int32), 0, dtype=torch.int32) - 1, torch.full((V,), -1, dtype=torch.int32, device=dev))
+    out_t = vmap[kept].to(torch.int32).reshape(-1, 3).contiguous()
+    out_v = vertices[used].contiguous()
+
+    def gathered(a):
+        return None if a is None else a.reshape(V, -1)[used].contiguous()
+    figures = torch.stack([(valid & ~exposed).sum(), ((present[:V] > 0) & (seen[:V] == 0)).sum()]).tolist()
+    report = dict(triangles_before=T, triangles_after=int(out_t.shape[0]), vertices_before=V, vertices_after=int(out_v.shape[0]),
+                  hidden_triangles=int(figures[0]), shells_before=topo["shells"], shells_dropped=int(figures[1]), totals=totals)
+    return dict(vertices=out_v, triangles=out_t, normals=gathered(normals), colors=gathered(colors), vertex_map=vmap, triangle_map=tmap,
+                counts=counts, report=report)
 
 
 def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, colors=None, bg_color=1.0, grid=None, texture=None,

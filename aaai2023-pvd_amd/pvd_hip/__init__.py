@@ -118,12 +118,15 @@ ENTRY_POINTS_MESH_WINDING = ("pvd_mesh_winding_workspace_bytes", "pvd_mesh_windi
                              "pvd_mesh_winding_lattice")
 # ... and the texture atlas of include/pvd_hip_mesh_tex.h (tests/test_abi_mesh_tex.py)
 ENTRY_POINTS_MESH_TEX = ("pvd_mesh_tex_layout", "pvd_mesh_tex_points", "pvd_mesh_tex_sample")
+# ... and the exposure query of csrc/pvd_hip_mesh_expose.h (tests/test_abi_mesh_expose.py)
+ENTRY_POINTS_MESH_EXPOSE = ("pvd_mesh_expose",)
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
-              + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING + ENTRY_POINTS_MESH_TEX):
+              + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING + ENTRY_POINTS_MESH_TEX
+              + ENTRY_POINTS_MESH_EXPOSE):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -1930,6 +1933,34 @@ def mesh_ray_cast(origins, dirs, T, G, pairs, workspace, t_min, t_max, t, tri, b
     _mesh_workspace(workspace, mesh_ray_workspace_bytes(T, G, pairs), "mesh_ray_workspace_bytes(T, G, pairs)")
     _call("pvd_mesh_ray_cast", dev, _p(origins), _p(dirs), _u32(N), _u32(T), _u32(G), _u64(pairs), _p(workspace),
           ctypes.c_size_t(workspace.numel()), _f32(t_min), _f32(t_max), _p(t), _p(tri), _p(bary))
+
+
+# --------------------------------------------------------------------------- exposure (csrc/pvd_hip_mesh_expose.h)
+MESH_EXPOSE_MAX_D = 1024  # PVD_MESH_EXPOSE_MAX_D: directions per call, 1 .. 1024
+MESH_EXPOSE_TOTALS = ("rays_cast", "rays_escaped", "front_exposed", "back_exposed", "hidden")  # the five totals of mesh_expose
+
+
+def mesh_expose(dirs, S, tri0, tri1, T, G, pairs, workspace, counts, totals):
+    """pvd_mesh_expose: counts [(tri1 - tri0), 4] int32 <- (front rays cast, front rays escaped, back rays cast, back rays escaped) of the
+    triangles tri0 .. tri1 - 1 of the mesh mesh_ray_build left in the workspace for the SAME T, G and pairs, over S (1 or 4) points per
+    triangle and the directions dirs [D,3] f32 (D 1 .. 1024); totals int64 [5] on the device += the band's MESH_EXPOSE_TOTALS (the
+    caller zeroes it before the first band)."""
+    dev = _dev(dirs, workspace, counts, totals)
+    _f32_all(dirs=dirs)
+    _want(counts, torch.int32, "counts")
+    _want(totals, torch.int64, "totals")
+    if dirs.dim() != 2 or dirs.shape[1] != 3 or not 1 <= int(dirs.shape[0]) <= MESH_EXPOSE_MAX_D:
+        raise PvdHipError("dirs must be [D,3] with D 1 .. %d" % MESH_EXPOSE_MAX_D)
+    if int(S) not in (1, 4):
+        raise PvdHipError("S must be 1 or 4, got %d" % int(S))
+    tri0, tri1 = int(tri0), int(tri1)
+    if not 0 <= tri0 <= tri1 <= int(T):
+        raise PvdHipError("the band must be 0 <= tri0 <= tri1 <= T, got %d .. %d of %d" % (tri0, tri1, int(T)))
+    if counts.numel() != 4 * (tri1 - tri0) or totals.numel() < 5:
+        raise PvdHipError("counts must hold 4 (tri1 - tri0) values and totals 5")
+    _mesh_workspace(workspace, mesh_ray_workspace_bytes(T, G, pairs), "mesh_ray_workspace_bytes(T, G, pairs)")
+    _call("pvd_mesh_expose", dev, _p(dirs), _u32(dirs.shape[0]), _u32(S), _u32(tri0), _u32(tri1), _u32(T), _u32(G), _u64(pairs), _p(workspace),
+          ctypes.c_size_t(workspace.numel()), _p(counts), _p(totals))
 
 
 # --------------------------------------------------------------------------- winding numbers (include/pvd_hip_mesh_winding.h)

@@ -7,6 +7,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
                               [--min-component N] [--largest-only] [--normals] [--colors] [--simplify G [--simplify-report]]
                               [--smooth N [--smooth-lambda L --smooth-mu M] [--smooth-report]] [--render-check N]
                               [--clean [--min-shell N] [--largest-shell-only]] [--topology-report] [--texture S]
+                              [--cull-hidden {shells,triangles} [--exposure-dirs D --exposure-samples S] [--exposure-report]]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
 The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
@@ -38,7 +39,15 @@ written (triangle, edge and shell counts, euler, closed, manifold); with --clean
 triangles, S 4 .. 64, the model's colour at the surface point of every texel) and writes an .obj, an .mtl and a .png next to the PLY.
 With --render-check N it prints the PSNR and SSIM of three renders against the model's own: the textured mesh, the same mesh with its
 vertex colours, and the full-resolution mesh (no --simplify) with its vertex colours -- what the texture wins back of what the
-simplification lost."""
+simplification lost.
+--cull-hidden shells|triangles drops the geometry no outside view can see (pvd/mesh.py: cull_hidden, csrc/mesh_expose.hip: rays from
+--exposure-samples 1 or 4 points of every triangle along --exposure-dirs D directions of a Fibonacci sphere, default 64; a triangle is
+exposed when a ray from its front escapes): `shells` drops a shell only when none of its triangles is exposed and keeps a closed mesh
+closed, `triangles` drops every unexposed triangle and opens the surface.  It runs after --smooth, --simplify and --clean and BEFORE the
+normals are recomputed, the colours are taken and the --texture atlas is baked -- that order is the point: a hidden triangle costs S^2 / 2
+texels and as many evaluations of the model.  (With it the colours are therefore those at the vertices of the final mesh.)
+--exposure-report prints one JSON line, cull_hidden's report: triangles and vertices before and after, hidden triangles, shells before
+and dropped, the ray totals; with --texture also atlas_before and atlas_after, [width, height] of the atlas without and with the cull."""
 import argparse
 import json
 import os
@@ -93,6 +102,39 @@ def render_check(model, m, views, res=200, textured=False):
     return meter.report(), (float(diff) / n if n else float("nan")), n
 
 
+@torch.no_grad()
+def cull_surface(model, m, mode, n_dirs=64, samples=1, colors=False, texture=0, from_faces=False):
+    """--cull-hidden: extract_surface's dict m (taken WITHOUT colours and texture) goes through cull_hidden (pvd/mesh.py,
+    csrc/mesh_expose.hip) with exposure_directions(n_dirs) and `samples` points per triangle; only then are the normals recomputed
+    (from_faces: face_vertex_normals of what is left, for a smoothed mesh; otherwise the normals it has follow the selection), the
+    colours taken (colors: vertex_colors at the vertices that are left) and the atlas baked (texture=S): hidden geometry costs neither
+    model evaluations nor texels.  vertex_map and triangle_map, where m has them, are composed with cull_hidden's.  Returns
+    cull_hidden's report, with mode, directions and samples, and with atlas_before / atlas_after = [width, height] where texture > 0."""
+    from pvd.mesh import bake_texture, cull_hidden, exposure_directions, face_vertex_normals, texture_layout, vertex_colors
+    T0 = int(m["triangles"].shape[0])
+    done = cull_hidden(m["vertices"], m["triangles"], normals=m["normals"], mode=mode,
+                       dirs=exposure_directions(n_dirs).to(m["vertices"].device), samples=samples)
+    report = dict(done["report"], mode=mode, directions=int(n_dirs), samples=int(samples))
+    for key in ("vertex_map", "triangle_map"):
+        first = m.get(key)
+        if first is not None:  # extracted -> simplified / cleaned -> culled
+            m[key] = torch.where(first >= 0, done[key][first.clamp(min=0).long()], torch.full_like(first, -1))
+        else:
+            m[key] = done[key]
+    m.update(vertices=done["vertices"], triangles=done["triangles"], normals=done["normals"], exposure=done["counts"])
+    if from_faces and m["normals"] is not None:
+        m["normals"] = face_vertex_normals(m["vertices"], m["triangles"])
+    if colors:
+        m["colors"] = vertex_colors(model, m["vertices"], m["normals"])
+    if int(texture) > 0:
+        for key, T in (("atlas_before", T0), ("atlas_after", int(m["triangles"].shape[0]))):
+            lay = texture_layout(T, int(texture))
+            report[key] = [lay["width"], lay["height"]]
+        baked = bake_texture(model, m["vertices"], m["triangles"], int(texture), normals=m["normals"])
+        m.update(texture=baked["texture"], uv=baked["uv"], texture_cell=int(texture))
+    return report
+
+
 def enclosed_volume(vertices, triangles):
     """The volume a closed mesh encloses: the sum of the signed tetrahedra (origin, a, b, c), float64 in torch."""
     c = vertices.to(torch.float64)[triangles.to(torch.int64)]  # [T,3,3]
@@ -126,7 +168,16 @@ def main():
     ap.add_argument("--topology-report", action="store_true", help="print mesh_topology of the mesh about to be written as JSON")
     ap.add_argument("--texture", type=int, default=0, metavar="S",
                     help="bake a texture atlas with S x S texels per pair of triangles (4 .. 64) and write .obj, .mtl and .png next to the PLY")
+    ap.add_argument("--cull-hidden", default=None, choices=["shells", "triangles"],
+                    help="drop what no outside view can see: whole unexposed shells, or every unexposed triangle (opens the surface)")
+    ap.add_argument("--exposure-dirs", type=int, default=64, metavar="D", help="with --cull-hidden: directions of the Fibonacci sphere (1 .. 1024)")
+    ap.add_argument("--exposure-samples", type=int, default=1, choices=[1, 4], metavar="S", help="with --cull-hidden: points per triangle (1 or 4)")
+    ap.add_argument("--exposure-report", action="store_true", help="with --cull-hidden: print cull_hidden's report as one JSON line")
     a = ap.parse_args()
+    if a.cull_hidden is None and (a.exposure_report or a.exposure_dirs != 64 or a.exposure_samples != 1):
+        ap.error("--exposure-dirs, --exposure-samples and --exposure-report need --cull-hidden")
+    if not 1 <= a.exposure_dirs <= 1024:
+        ap.error("--exposure-dirs must be 1 .. 1024")
     if (a.min_shell > 0 or a.largest_shell_only) and not a.clean:
         ap.error("--min-shell and --largest-shell-only need --clean")
     if a.render_check > 0 and not (a.colors or a.texture > 0):
@@ -144,10 +195,15 @@ def main():
               smooth_lambda=a.smooth_lambda, smooth_mu=a.smooth_mu, clean=a.clean, min_shell_triangles=a.min_shell,
               largest_shell_only=a.largest_shell_only)
     compare = a.texture > 0 and a.render_check > 0  # the three renders need the vertex colours too, written or not
-    m = extract_surface(model, normals=a.normals, colors=a.colors or compare, simplify=a.simplify,
-                        **(dict(texture=a.texture) if a.texture > 0 else {}), **kw)
+    if a.cull_hidden:  # the geometry first; normals for the colours' sake too; colours and texture after the cull
+        m = extract_surface(model, normals=a.normals or a.colors or compare, colors=False, simplify=a.simplify, **kw)
+        exposure = cull_surface(model, m, a.cull_hidden, a.exposure_dirs, a.exposure_samples, colors=a.colors or compare, texture=a.texture,
+                                from_faces=a.smooth > 0)
+    else:
+        m = extract_surface(model, normals=a.normals, colors=a.colors or compare, simplify=a.simplify,
+                            **(dict(texture=a.texture) if a.texture > 0 else {}), **kw)
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
-    write_ply(out, m["vertices"], m["triangles"], normals=m["normals"], colors=m["colors"] if a.colors else None)
+    write_ply(out, m["vertices"], m["triangles"], normals=m["normals"] if a.normals else None, colors=m["colors"] if a.colors else None)
     carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
     print("%s: %d vertices (%s), %d triangles at density %.6g, resolution %d"
           % (out, m["vertices"].shape[0], carries, m["triangles"].shape[0], thresh, a.resolution))
@@ -178,13 +234,19 @@ def main():
         print("clean: %d -> %d triangles (%d invalid, %d duplicate, %d cancelled), %d -> %d shells"
               % (before["valid"] + before["invalid"], after["survivors"], before["invalid"], before["duplicate"], before["cancelled"],
                  before["shells"], after["shells"]))
+    if a.cull_hidden:
+        print("cull hidden (%s, %d directions, %d per triangle): %d -> %d triangles, %d -> %d vertices, %d of %d shells dropped"
+              % (a.cull_hidden, a.exposure_dirs, a.exposure_samples, exposure["triangles_before"], exposure["triangles_after"],
+                 exposure["vertices_before"], exposure["vertices_after"], exposure["shells_dropped"], exposure["shells_before"]))
+        if a.exposure_report:
+            print(json.dumps(exposure))
     if a.topology_report:
         for top in ((m["topology"]["before"], m["topology"]["after"]) if a.clean else (mesh_topology(m["vertices"], m["triangles"]),)):
             print(json.dumps(top))
     if a.texture > 0:
         stem = os.path.splitext(out)[0]
         write_png(stem + ".png", m["texture"])
-        write_obj(stem + ".obj", m["vertices"], m["triangles"], m["uv"], os.path.basename(stem + ".png"), normals=m["normals"])
+        write_obj(stem + ".obj", m["vertices"], m["triangles"], m["uv"], os.path.basename(stem + ".png"), normals=m["normals"] if a.normals else None)
         print("%s.obj, .mtl, .png: texture %d x %d, %d x %d texels per pair of triangles"
               % (stem, m["texture"].shape[1], m["texture"].shape[0], a.texture, a.texture))
     if compare:
