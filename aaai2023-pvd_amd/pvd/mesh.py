@@ -172,7 +172,7 @@ def vertex_colors(model, vertices, normals, chunk=1 << 20, autocast=True):
 
 def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, min_points=0, largest_only=False,
                     normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, clean=False,
-                    min_shell_triangles=0, largest_shell_only=False, texture=0):
+                    min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0):
     """extract_geometry with what a viewer needs next to the geometry, as a dict: vertices, triangles, normals (extract_mesh's
     with_normals) and colors (vertex_colors), None where not asked for; field (the density volume, filtered where min_points > 0
     or largest_only), threshold, and counts = (components found, components kept, points kept), None where nothing was filtered.
@@ -189,7 +189,10 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
     texture=S > 0: an atlas with S x S texels per pair of triangles is baked last (bake_texture: the model's colour head at the surface
     point of every texel, seen along the mesh's normals, or the face normals where none were asked for), on the final mesh -- after
     the smoothing, the simplification and the clean-up; the dict then also holds texture [Ht,Wt,3], uv [T,3,2] and texture_cell = S.
-    texture=0: the dict is what it was."""
+    texture=0: the dict is what it was.
+    texture_sh=L > 0 with texture=S > 0: bake_sh_texture (L bands of spherical harmonics per texel, the colour as a function of the
+    view) in place of the flat bake; the dict then holds texture [Ht,Wt,L*L,3], texture_degree = L and texture_diffuse [Ht,Wt,3], the
+    view-independent part, next to uv and texture_cell.  texture_sh=0: the dict is what it was."""
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -227,7 +230,11 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
             vmap = torch.where(first >= 0, vmap[first.clamp(min=0).long()], torch.full_like(first, -1))
         out.update(vertices=done["vertices"], triangles=done["triangles"], normals=done["normals"], colors=done["colors"],
                    vertex_map=vmap, triangle_map=done["triangle_map"], topology=dict(before=done["before"], after=done["after"]))
-    if int(texture) > 0:
+    if int(texture) > 0 and int(texture_sh) > 0:
+        baked = bake_sh_texture(model, out["vertices"], out["triangles"], int(texture), degree=int(texture_sh), normals=out["normals"])
+        out.update(texture=baked["texture"], uv=baked["uv"], texture_cell=int(texture), texture_degree=int(texture_sh),
+                   texture_diffuse=baked["diffuse"])
+    elif int(texture) > 0:
         baked = bake_texture(model, out["vertices"], out["triangles"], int(texture), normals=out["normals"])
         out.update(texture=baked["texture"], uv=baked["uv"], texture_cell=int(texture))
     return out
@@ -744,7 +751,8 @@ def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, color
         color [H,W,3]       the barycentric mean of the vertex colours [V,3] over bg_color (a float or 3 floats); None without colors
     The interpolation is plain torch gathers on the cast's output.
     texture [Ht,Wt,3] with texture_cell = S (bake_texture's, for these triangles): color is sample_texture's bilinear lookup of the
-    atlas at the hits instead (csrc/mesh_tex.hip), whatever colors holds."""
+    atlas at the hits instead (csrc/mesh_tex.hip), whatever colors holds.  A 4-D texture [Ht,Wt,K,3] (bake_sh_texture's) is an SH atlas:
+    color is sample_sh_texture's, evaluated at each ray's direction (csrc/mesh_shtex.hip); K gives the number of bands."""
     from .scene import get_rays
     dev = vertices.device
     pose = torch.as_tensor(pose, dtype=torch.float32, device=dev).reshape(4, 4)
@@ -783,7 +791,10 @@ def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, color
     if texture is not None:
         if texture_cell is None:
             raise ValueError("texture needs texture_cell, the cell edge S it was baked with")
-        col = sample_texture(texture, texture_cell, int(triangles.shape[0]), tri, bary, bg_color=bg_color).reshape(H, W, 3)
+        if texture.dim() == 4:
+            col = sample_sh_texture(texture, texture_cell, int(triangles.shape[0]), tri, bary, d, bg_color=bg_color).reshape(H, W, 3)
+        else:
+            col = sample_texture(texture, texture_cell, int(triangles.shape[0]), tri, bary, bg_color=bg_color).reshape(H, W, 3)
     return dict(depth=torch.where(mask, t, torch.zeros_like(t)).reshape(H, W), mask=mask.reshape(H, W), tri=tri.reshape(H, W),
                 bary=bary.reshape(H, W, 2), normal=nrm.reshape(H, W, 3), color=col)
 
@@ -794,7 +805,8 @@ def evaluate_mesh_views(vertices, triangles, colors, poses, intrinsics, H, W, tr
     """Render the coloured mesh from poses [P,4,4] (render_mesh) and measure each view's colour image against `truth` the way
     pvd.metrics.evaluate_views does for a model: a tensor [P,H,W,3], or a callable (rays_o, rays_d) -> [H*W,3].  Returns
     ImageMeter.report() plus "coverage", the share of all pixels that hit the mesh (and, with keep_images, the views under
-    "images").  texture, texture_cell: render_mesh's -- the views are coloured from the atlas, and colors may be None."""
+    "images").  texture, texture_cell: render_mesh's -- the views are coloured from the atlas (a flat one, or a 4-D SH atlas seen along
+    each view's rays), and colors may be None."""
     from .metrics import ImageMeter
     from .scene import get_rays
     meter = ImageMeter()
@@ -1179,3 +1191,166 @@ def read_obj(path):
                 triangles=torch.from_numpy(np.array(fv, np.int32).reshape(-1, 3)), uv=torch.from_numpy(vt[ft].reshape(-1, 3, 2)),
                 normals=torch.from_numpy(np.array(vn, np.float32).reshape(-1, 3)) if vn else None, mtllib=mtllib,
                 texture_file=texture_file)
+
+
+# ------------------------------------------------------------------------------------------------ view-dependent texture atlases
+_SH_Y0 = 0.282094806  # Y_0 of csrc/pvd_hip_mesh_shtex.h
+
+
+def _sh_bands(degree):
+    L = int(degree)
+    if not 1 <= L <= 4:
+        raise ValueError("degree (the number of SH bands) must be 1 .. 4, got %r" % (degree,))
+    return L
+
+
+def _sh_basis_host(d, L):
+    """The header's sixteen polynomials on a host tensor: the same float32 operations in the same order, each a torch operation of its
+    own (eager torch fuses nothing)."""
+    x, y, z = d[:, 0], d[:, 1], d[:, 2]
+
+    def c(v):
+        return torch.tensor(v, dtype=torch.float32)
+    Y = [c(0.282094806).expand(d.shape[0])]
+    if L > 1:
+        Y += [c(-0.488602519) * y, c(0.488602519) * z, c(-0.488602519) * x]
+    if L > 2:
+        xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
+        Y += [c(1.09254849) * xy, c(-1.09254849) * yz, c(0.946174681) * zz - c(0.31539157), c(-1.09254849) * xz,
+              c(0.546274245) * (xx - yy)]
+    if L > 3:
+        Y += [c(-0.590043604) * (y * (c(3.0) * xx - yy)), c(2.89061141) * (xy * z), (c(0.457045794) - c(2.28522897) * zz) * y,
+              (c(1.86588168) * zz - c(1.11952901)) * z, (c(0.457045794) - c(2.28522897) * zz) * x, c(1.44530571) * (z * (xx - yy)),
+              c(-0.590043604) * (x * (xx - c(3.0) * yy))]
+    return torch.stack(Y, dim=1)
+
+
+def sh_basis(dirs, degree):
+    """[N, K] f32, K = degree^2: the real spherical harmonics of csrc/pvd_hip_mesh_shtex.h (index l * l + l + m, the signs of the
+    direction encoder's basis) at dirs [N,3], used as given and not normalised.  A device tensor goes through the kernel
+    (csrc/mesh_shtex.hip); a host tensor -- the few dozen fitting directions of sh_fit_matrix -- is evaluated on the host by the same
+    float32 operations in the same order, so both give the same bits."""
+    L = _sh_bands(degree)
+    dirs = dirs.to(torch.float32).reshape(-1, 3).contiguous()
+    if not dirs.is_cuda:
+        return _sh_basis_host(dirs, L)
+    import pvd_hip
+    out = torch.empty(int(dirs.shape[0]), L * L, dtype=torch.float32, device=dirs.device)
+    pvd_hip.mesh_shtex_basis(dirs, L, out)
+    return out
+
+
+def sh_fit_matrix(dirs, degree):
+    """P [K, D] f32 on dirs' device: the least-squares fit of K = degree^2 SH coefficients to values at the D directions dirs [D,3] --
+    the pseudo-inverse of Y = sh_basis(dirs, degree) [D,K], taken in float64 on the host and rounded once.  ValueError where D < K, and
+    where Y's smallest singular value is below 1e-3 of its largest: a degenerate set (directions in a plane, say) would otherwise bake
+    coefficients that mean nothing."""
+    import numpy as np
+    L = _sh_bands(degree)
+    K = L * L
+    D = int(dirs.reshape(-1, 3).shape[0])
+    if D < K:
+        raise ValueError("%d directions cannot fit %d coefficients" % (D, K))
+    Y = sh_basis(dirs, L).to(torch.float64).cpu().numpy()
+    sv = np.linalg.svd(Y, compute_uv=False)
+    if not np.all(np.isfinite(sv)) or sv[-1] < 1e-3 * sv[0]:
+        raise ValueError("the directions do not determine %d SH coefficients: singular values %.3g .. %.3g" % (K, sv[-1], sv[0]))
+    return torch.from_numpy(np.linalg.pinv(Y).astype(np.float32)).to(dirs.device)
+
+
+def _colors_along(model, x, d, chunk, autocast=True):
+    """[M,3] f32 in [0,1]: rgb = model(x, d)[1], the colour head seen along the direction of travel d, as vertex_colors asks it with
+    d = -normal.  Rows that are not finite never reach the model and get the colour 0."""
+    M = int(x.shape[0])
+    out = torch.empty(M, 3, dtype=torch.float32, device=x.device)
+    aabb = model.aabb_infer.to(device=x.device, dtype=torch.float32)
+    centre = (aabb[:3] + aabb[3:]) * 0.5
+    down = torch.tensor([0.0, 0.0, -1.0], device=x.device)
+    for s in range(0, M, int(chunk)):
+        xs, ds = x[s:s + int(chunk)], d[s:s + int(chunk)]
+        bad = ~(torch.isfinite(xs).all(dim=1) & torch.isfinite(ds).all(dim=1))
+        xs = torch.where(bad[:, None], centre[None, :], xs).contiguous()
+        ds = torch.where(bad[:, None], down[None, :], ds).contiguous()
+        with torch.autocast("cuda", dtype=torch.float16, enabled=bool(autocast)):
+            rgb = model(xs, ds)[1]
+        out[s:s + xs.shape[0]] = torch.where(bad[:, None], torch.zeros_like(xs), rgb.to(torch.float32).clamp(0.0, 1.0))
+    return out
+
+
+@torch.no_grad()
+def bake_sh_texture(source, vertices, triangles, S, degree=3, dirs=None, normals=None, chunk=1 << 20, batch=8):
+    """dict(texture [Ht,Wt,K,3] f32, uv [T,3,2] f32, layout, degree, diffuse [Ht,Wt,3] f32): per texel of the mesh's atlas
+    (texture_layout, texture_points) the K = degree^2 SH coefficients per channel of the colour of `source` as a function of the
+    direction of travel d of a ray that sees the texel's surface point (csrc/pvd_hip_mesh_shtex.h).  dirs [D,3]: the fitting
+    directions, one full-sphere set for every texel (default exposure_directions(64)); a direction that would look at a texel from
+    behind is mirrored in its tangent plane, so no colour is taken from behind the surface.  source: a model -- rgb = model(x, d)[1],
+    the colour head as vertex_colors asks it -- or a callable (x [M,3], d [M,3]) -> [M,3].  The bake costs D colour queries per texel:
+    in bands of whole image rows of about `chunk` texels and `batch` directions at a time, projected onto the basis as they come
+    (sh_fit_matrix).  Texels nothing owns, and those of invalid triangles, get all-zero coefficients and never reach the source.
+    diffuse = clamp(coef[..., 0, :] * Y_0, 0, 1), the view-independent part: what an OBJ / PNG can carry.  sample_sh_texture and
+    render_mesh(texture=...) evaluate the atlas at a ray's direction."""
+    import pvd_hip
+    L = _sh_bands(degree)
+    K = L * L
+    dev = vertices.device
+    T = int(triangles.reshape(-1, 3).shape[0])
+    lay = texture_layout(T, S)
+    Wt, Ht = lay["width"], lay["height"]
+    U = (exposure_directions(64) if dirs is None else dirs).to(torch.float32).reshape(-1, 3)
+    P = sh_fit_matrix(U, L).to(dev)
+    U = U.to(dev).contiguous()
+    D, batch = int(U.shape[0]), max(1, int(batch))
+    texture = torch.empty(Ht, Wt, K, 3, dtype=torch.float32, device=dev)
+    band = max(1, int(chunk) // Wt)
+    is_model = hasattr(source, "aabb_infer")
+    for row0 in range(0, Ht, band):
+        row1 = min(row0 + band, Ht)
+        x, n = texture_points(vertices, triangles, S, normals=normals, rows=(row0, row1))
+        good = torch.isfinite(x).all(dim=1) & torch.isfinite(n).all(dim=1)
+        rows = torch.zeros(int(x.shape[0]), K, 3, dtype=torch.float32, device=dev)
+        xg, ng = x[good].contiguous(), n[good].contiguous()
+        M = int(xg.shape[0])
+        if M:
+            coef = torch.empty(M, K, 3, dtype=torch.float32, device=dev)
+            for j0 in range(0, D, batch):
+                Uj = U[j0:j0 + batch].contiguous()
+                J = int(Uj.shape[0])
+                d = torch.empty(J, M, 3, dtype=torch.float32, device=dev)
+                pvd_hip.mesh_shtex_dirs(ng, Uj, d)
+                xq = xg[None].expand(J, M, 3).reshape(-1, 3)
+                if is_model:
+                    rgb = _colors_along(source, xq, d.reshape(-1, 3), chunk)
+                else:
+                    rgb = source(xq.contiguous(), d.reshape(-1, 3)).to(torch.float32)
+                pvd_hip.mesh_shtex_project(rgb.reshape(J, M, 3).contiguous(), P[:, j0:j0 + J].contiguous(), L, coef, j0 == 0)
+            rows[good] = coef
+        texture[row0:row1] = rows.reshape(row1 - row0, Wt, K, 3)
+    diffuse = (texture[:, :, 0, :] * torch.tensor(_SH_Y0, dtype=torch.float32, device=dev)).clamp(0.0, 1.0)
+    return dict(texture=texture, uv=texture_uv(T, S, device=dev), layout=lay, degree=L, diffuse=diffuse)
+
+
+def sample_sh_texture(texture, S, T, tri, bary, dirs, bg_color=1.0):
+    """[..., 3] f32 in [0,1] on the device: the SH atlas texture [Ht,Wt,K,3] (bake_sh_texture's, T triangles at the cell edge S)
+    evaluated at the directions dirs [..., 3] of the rays and looked up bilinearly at their hits (tri [...] int32, bary [..., 2] f32,
+    mesh_raycast's); bg_color (a float or 3 floats) where tri is -1.  K = 1, 4, 9 or 16 gives the number of bands.  Reads the hit
+    triangle's own cell only (csrc/pvd_hip_mesh_shtex.h; csrc/mesh_shtex.hip)."""
+    import math
+
+    import pvd_hip
+    if texture.dim() != 4:
+        raise ValueError("an SH atlas is [Ht,Wt,K,3]")
+    K = int(texture.shape[2])
+    L = math.isqrt(K)
+    if L * L != K:
+        raise ValueError("K = %d coefficients per channel is not a square" % K)
+    L = _sh_bands(L)
+    dev = texture.device
+    texture = texture.to(torch.float32).contiguous()
+    shape = tuple(tri.shape)
+    tri = tri.to(torch.int32).reshape(-1).contiguous()
+    bary = bary.to(torch.float32).reshape(-1, 2).contiguous()
+    dirs = dirs.to(torch.float32).reshape(-1, 3).contiguous()
+    bg = torch.as_tensor(bg_color, dtype=torch.float32, device=dev).expand(3).contiguous()
+    color = torch.empty(int(tri.shape[0]), 3, dtype=torch.float32, device=dev)
+    pvd_hip.mesh_shtex_sample(texture, int(T), int(S), L, tri, bary, dirs, bg, color)
+    return color.reshape(shape + (3,))

@@ -120,13 +120,15 @@ ENTRY_POINTS_MESH_WINDING = ("pvd_mesh_winding_workspace_bytes", "pvd_mesh_windi
 ENTRY_POINTS_MESH_TEX = ("pvd_mesh_tex_layout", "pvd_mesh_tex_points", "pvd_mesh_tex_sample")
 # ... and the exposure query of csrc/pvd_hip_mesh_expose.h (tests/test_abi_mesh_expose.py)
 ENTRY_POINTS_MESH_EXPOSE = ("pvd_mesh_expose",)
+# ... and the view-dependent atlas of csrc/pvd_hip_mesh_shtex.h (tests/test_abi_mesh_shtex.py)
+ENTRY_POINTS_MESH_SHTEX = ("pvd_mesh_shtex_basis", "pvd_mesh_shtex_dirs", "pvd_mesh_shtex_project", "pvd_mesh_shtex_sample")
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
               + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING + ENTRY_POINTS_MESH_TEX
-              + ENTRY_POINTS_MESH_EXPOSE):
+              + ENTRY_POINTS_MESH_EXPOSE + ENTRY_POINTS_MESH_SHTEX):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -2099,6 +2101,68 @@ def mesh_tex_sample(texture, T, S, tri, bary, bg3, color):
     if bary.numel() != 2 * N or color.numel() != 3 * N or bg3.numel() < 3:
         raise PvdHipError("bary must hold 2 N, color 3 N and bg3 3 values")
     _call("pvd_mesh_tex_sample", dev, _p(texture), _u32(T), _u32(S), _p(tri), _p(bary), _u32(N), _p(bg3), _p(color))
+
+
+# --------------------------------------------------------------------------- view-dependent atlas (csrc/pvd_hip_mesh_shtex.h)
+MESH_SHTEX_MAX_L = 4  # PVD_MESH_SHTEX_MAX_L: the largest number of bands; K = L * L coefficients per channel
+
+
+def _shtex_bands(L):
+    if not 1 <= int(L) <= MESH_SHTEX_MAX_L:
+        raise PvdHipError("the number of SH bands must be 1 .. %d, got %d" % (MESH_SHTEX_MAX_L, int(L)))
+    return int(L)
+
+
+def mesh_shtex_basis(dirs, L, out):
+    """pvd_mesh_shtex_basis: out [N, L*L] f32 <- the header's real SH basis of dirs [N,3] f32, used as given (not normalised)."""
+    dev = _dev(dirs, out)
+    _f32_all(dirs=dirs, out=out)
+    L = _shtex_bands(L)
+    if dirs.dim() != 2 or dirs.shape[1] != 3 or tuple(out.shape) != (int(dirs.shape[0]), L * L):
+        raise PvdHipError("dirs must be [N,3] and out [N,%d]" % (L * L))
+    _call("pvd_mesh_shtex_basis", dev, _p(dirs), _u32(dirs.shape[0]), _u32(L), _p(out))
+
+
+def mesh_shtex_dirs(n, U, d):
+    """pvd_mesh_shtex_dirs: d [J,M,3] f32 <- the fitting directions U [J,3] f32, mirrored in the tangent plane of the normals n [M,3] f32
+    (mesh_tex_points': unnormalised, NaN allowed) where they would look at the surface from behind."""
+    dev = _dev(n, U, d)
+    _f32_all(n=n, U=U, d=d)
+    if n.dim() != 2 or n.shape[1] != 3 or U.dim() != 2 or U.shape[1] != 3 or tuple(d.shape) != (int(U.shape[0]), int(n.shape[0]), 3):
+        raise PvdHipError("n must be [M,3], U [J,3] and d [J,M,3]")
+    _call("pvd_mesh_shtex_dirs", dev, _p(n), _u32(n.shape[0]), _p(U), _u32(U.shape[0]), _p(d))
+
+
+def mesh_shtex_project(rgb, Pcols, L, coef, first):
+    """pvd_mesh_shtex_project: coef [M, L*L, 3] f32 (from +0 where first, else from coef) += Pcols [L*L, J] f32 applied to rgb [J,M,3] f32,
+    direction after direction in the header's order."""
+    dev = _dev(rgb, Pcols, coef)
+    _f32_all(rgb=rgb, Pcols=Pcols, coef=coef)
+    L = _shtex_bands(L)
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise PvdHipError("rgb must be [J,M,3]")
+    J, M = int(rgb.shape[0]), int(rgb.shape[1])
+    if tuple(Pcols.shape) != (L * L, J) or tuple(coef.shape) != (M, L * L, 3):
+        raise PvdHipError("Pcols must be [%d,%d] and coef [%d,%d,3]" % (L * L, J, M, L * L))
+    _call("pvd_mesh_shtex_project", dev, _p(rgb), _p(Pcols), _u32(L), _u32(J), _u32(M), _p(coef), _u32(1 if first else 0))
+
+
+def mesh_shtex_sample(texture, T, S, L, tri, bary, dirs, bg3, color):
+    """pvd_mesh_shtex_sample: color [N,3] f32 <- the SH atlas texture [Ht,Wt,L*L,3] f32 (T triangles, cell edge S) evaluated at the
+    directions dirs [N,3] f32 and looked up bilinearly at tri [N] int32, bary [N,2] f32, clamped to [0, 1]; bg3 (device f32 [3]) where
+    tri is outside 0 .. T - 1."""
+    dev = _dev(texture, tri, bary, dirs, bg3, color)
+    _f32_all(texture=texture, bary=bary, dirs=dirs, bg3=bg3, color=color)
+    _want(tri, torch.int32, "tri")
+    L = _shtex_bands(L)
+    Wt, Ht = mesh_tex_layout(T, S)[2:]
+    if tuple(texture.shape) != (Ht, Wt, L * L, 3):
+        raise PvdHipError("texture must be [%d,%d,%d,3] for T=%d S=%d L=%d, got %s"
+                          % (Ht, Wt, L * L, int(T), int(S), L, tuple(texture.shape)))
+    N = int(tri.numel())
+    if bary.numel() != 2 * N or dirs.numel() != 3 * N or color.numel() != 3 * N or bg3.numel() < 3:
+        raise PvdHipError("bary must hold 2 N, dirs and color 3 N and bg3 3 values")
+    _call("pvd_mesh_shtex_sample", dev, _p(texture), _u32(T), _u32(S), _u32(L), _p(tri), _p(bary), _p(dirs), _u32(N), _p(bg3), _p(color))
 
 
 # --------------------------------------------------------------------------- Taubin smoothing (include/pvd_hip_mesh_smooth.h)

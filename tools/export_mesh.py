@@ -6,7 +6,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
   python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
                               [--min-component N] [--largest-only] [--normals] [--colors] [--simplify G [--simplify-report]]
                               [--smooth N [--smooth-lambda L --smooth-mu M] [--smooth-report]] [--render-check N]
-                              [--clean [--min-shell N] [--largest-shell-only]] [--topology-report] [--texture S]
+                              [--clean [--min-shell N] [--largest-shell-only]] [--topology-report] [--texture S [--texture-sh L]]
                               [--cull-hidden {shells,triangles} [--exposure-dirs D --exposure-samples S] [--exposure-report]]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
@@ -47,12 +47,18 @@ closed, `triangles` drops every unexposed triangle and opens the surface.  It ru
 normals are recomputed, the colours are taken and the --texture atlas is baked -- that order is the point: a hidden triangle costs S^2 / 2
 texels and as many evaluations of the model.  (With it the colours are therefore those at the vertices of the final mesh.)
 --exposure-report prints one JSON line, cull_hidden's report: triangles and vertices before and after, hidden triangles, shells before
-and dropped, the ray totals; with --texture also atlas_before and atlas_after, [width, height] of the atlas without and with the cull."""
+and dropped, the ray totals; with --texture also atlas_before and atlas_after, [width, height] of the atlas without and with the cull.
+--texture-sh L (1 .. 4, needs --texture S) bakes a view-dependent atlas instead (pvd/mesh.py: bake_sh_texture, csrc/mesh_shtex.hip): L * L
+spherical-harmonics coefficients per channel and texel, fitted to the model's colour along 64 directions.  The .png / .obj / .mtl are
+written from its view-independent part; the coefficients go to <stem>.shtex.npy ([height, width, L * L, 3] float32, numpy.save) with a
+one-line JSON sidecar <stem>.shtex.json carrying S, L and T.  With --render-check N a fourth render is reported next to the three: the
+SH-textured mesh, coloured at every pixel for that pixel's ray (the flat atlas of the first line is then baked as well, for the check only)."""
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,15 +66,16 @@ sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
 
 from pvd.checkpoint import load_student_checkpoint  # noqa: E402
 from pvd.config import PVDConfig  # noqa: E402
-from pvd.mesh import (compare_meshes, default_threshold, extract_mesh, extract_surface, mesh_topology, render_mesh, smooth_mesh,  # noqa: E402
+from pvd.mesh import (bake_texture, compare_meshes, default_threshold, extract_mesh, extract_surface, mesh_topology, render_mesh, smooth_mesh,  # noqa: E402
                       write_obj, write_ply, write_png)
 from pvd.ops import hip_ops  # noqa: E402
 from pvd.workload import make_model  # noqa: E402
 
 
 @torch.no_grad()
-def render_check(model, m, views, res=200, textured=False):
-    """textured: the mesh is coloured from m["texture"] (render_mesh's texture) instead of m["colors"].
+def render_check(model, m, views, res=200, textured=False, texture=None):
+    """textured: the mesh is coloured from m["texture"] (render_mesh's texture; `texture` where given: a flat or an SH atlas at the
+    cell edge m["texture_cell"]) instead of m["colors"].
     (ImageMeter report of the mesh's colour image against the model's render, mean |depth difference| over the pixels both hit,
     their number), over `views` pose_spherical cameras on a circle at the reference's radius and scale.  Depths in world units along
     the ray: the model's normalised depth d is turned back into near + d (far - near) with the near / far of its own slab test."""
@@ -82,8 +89,8 @@ def render_check(model, m, views, res=200, textured=False):
     for q in range(views):
         pose = torch.from_numpy(nerf_matrix_to_ngp(pose_spherical(-180.0 + 360.0 * q / views, -30.0, 4.0)).astype(np.float32)).to(dev)
         if textured:
-            mesh = render_mesh(m["vertices"], m["triangles"], pose, intr, res, res, bg_color=1.0, texture=m["texture"],
-                               texture_cell=m["texture_cell"])
+            mesh = render_mesh(m["vertices"], m["triangles"], pose, intr, res, res, bg_color=1.0,
+                               texture=m["texture"] if texture is None else texture, texture_cell=m["texture_cell"])
         else:
             mesh = render_mesh(m["vertices"], m["triangles"], pose, intr, res, res, colors=m["colors"], bg_color=1.0)
         r = get_rays(pose[None], intr, res, res, -1)
@@ -103,14 +110,15 @@ def render_check(model, m, views, res=200, textured=False):
 
 
 @torch.no_grad()
-def cull_surface(model, m, mode, n_dirs=64, samples=1, colors=False, texture=0, from_faces=False):
+def cull_surface(model, m, mode, n_dirs=64, samples=1, colors=False, texture=0, from_faces=False, texture_sh=0):
     """--cull-hidden: extract_surface's dict m (taken WITHOUT colours and texture) goes through cull_hidden (pvd/mesh.py,
     csrc/mesh_expose.hip) with exposure_directions(n_dirs) and `samples` points per triangle; only then are the normals recomputed
     (from_faces: face_vertex_normals of what is left, for a smoothed mesh; otherwise the normals it has follow the selection), the
     colours taken (colors: vertex_colors at the vertices that are left) and the atlas baked (texture=S): hidden geometry costs neither
     model evaluations nor texels.  vertex_map and triangle_map, where m has them, are composed with cull_hidden's.  Returns
-    cull_hidden's report, with mode, directions and samples, and with atlas_before / atlas_after = [width, height] where texture > 0."""
-    from pvd.mesh import bake_texture, cull_hidden, exposure_directions, face_vertex_normals, texture_layout, vertex_colors
+    cull_hidden's report, with mode, directions and samples, and with atlas_before / atlas_after = [width, height] where texture > 0.
+    texture_sh=L > 0: the atlas is bake_sh_texture's, under the keys extract_surface(texture_sh=L) uses."""
+    from pvd.mesh import bake_sh_texture, bake_texture, cull_hidden, exposure_directions, face_vertex_normals, texture_layout, vertex_colors
     T0 = int(m["triangles"].shape[0])
     done = cull_hidden(m["vertices"], m["triangles"], normals=m["normals"], mode=mode,
                        dirs=exposure_directions(n_dirs).to(m["vertices"].device), samples=samples)
@@ -130,7 +138,11 @@ def cull_surface(model, m, mode, n_dirs=64, samples=1, colors=False, texture=0, 
         for key, T in (("atlas_before", T0), ("atlas_after", int(m["triangles"].shape[0]))):
             lay = texture_layout(T, int(texture))
             report[key] = [lay["width"], lay["height"]]
-        baked = bake_texture(model, m["vertices"], m["triangles"], int(texture), normals=m["normals"])
+        if int(texture_sh) > 0:
+            baked = bake_sh_texture(model, m["vertices"], m["triangles"], int(texture), degree=int(texture_sh), normals=m["normals"])
+            m.update(texture_degree=int(texture_sh), texture_diffuse=baked["diffuse"])
+        else:
+            baked = bake_texture(model, m["vertices"], m["triangles"], int(texture), normals=m["normals"])
         m.update(texture=baked["texture"], uv=baked["uv"], texture_cell=int(texture))
     return report
 
@@ -168,6 +180,9 @@ def main():
     ap.add_argument("--topology-report", action="store_true", help="print mesh_topology of the mesh about to be written as JSON")
     ap.add_argument("--texture", type=int, default=0, metavar="S",
                     help="bake a texture atlas with S x S texels per pair of triangles (4 .. 64) and write .obj, .mtl and .png next to the PLY")
+    ap.add_argument("--texture-sh", type=int, default=0, metavar="L",
+                    help="with --texture S: bake L * L spherical-harmonics coefficients per texel (1 .. 4), the colour as a function of the view; "
+                         "writes <stem>.shtex.npy and .shtex.json next to the .png, which holds the view-independent part")
     ap.add_argument("--cull-hidden", default=None, choices=["shells", "triangles"],
                     help="drop what no outside view can see: whole unexposed shells, or every unexposed triangle (opens the surface)")
     ap.add_argument("--exposure-dirs", type=int, default=64, metavar="D", help="with --cull-hidden: directions of the Fibonacci sphere (1 .. 1024)")
@@ -180,6 +195,8 @@ def main():
         ap.error("--exposure-dirs must be 1 .. 1024")
     if (a.min_shell > 0 or a.largest_shell_only) and not a.clean:
         ap.error("--min-shell and --largest-shell-only need --clean")
+    if a.texture_sh != 0 and (a.texture <= 0 or not 1 <= a.texture_sh <= 4):
+        ap.error("--texture-sh must be 1 .. 4 and needs --texture S")
     if a.render_check > 0 and not (a.colors or a.texture > 0):
         ap.error("--render-check needs --colors or --texture")
     dev = torch.device("cuda:0")
@@ -198,10 +215,11 @@ def main():
     if a.cull_hidden:  # the geometry first; normals for the colours' sake too; colours and texture after the cull
         m = extract_surface(model, normals=a.normals or a.colors or compare, colors=False, simplify=a.simplify, **kw)
         exposure = cull_surface(model, m, a.cull_hidden, a.exposure_dirs, a.exposure_samples, colors=a.colors or compare, texture=a.texture,
-                                from_faces=a.smooth > 0)
+                                from_faces=a.smooth > 0, texture_sh=a.texture_sh)
     else:
         m = extract_surface(model, normals=a.normals, colors=a.colors or compare, simplify=a.simplify,
-                            **(dict(texture=a.texture) if a.texture > 0 else {}), **kw)
+                            **(dict(texture=a.texture) if a.texture > 0 else {}), **(dict(texture_sh=a.texture_sh) if a.texture_sh > 0 else {}),
+                            **kw)
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
     write_ply(out, m["vertices"], m["triangles"], normals=m["normals"] if a.normals else None, colors=m["colors"] if a.colors else None)
     carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
@@ -245,14 +263,26 @@ def main():
             print(json.dumps(top))
     if a.texture > 0:
         stem = os.path.splitext(out)[0]
-        write_png(stem + ".png", m["texture"])
+        write_png(stem + ".png", m["texture_diffuse"] if a.texture_sh > 0 else m["texture"])
         write_obj(stem + ".obj", m["vertices"], m["triangles"], m["uv"], os.path.basename(stem + ".png"), normals=m["normals"] if a.normals else None)
         print("%s.obj, .mtl, .png: texture %d x %d, %d x %d texels per pair of triangles"
               % (stem, m["texture"].shape[1], m["texture"].shape[0], a.texture, a.texture))
+        if a.texture_sh > 0:
+            np.save(stem + ".shtex.npy", m["texture"].cpu().numpy())
+            with open(stem + ".shtex.json", "w") as f:
+                f.write(json.dumps(dict(S=a.texture, L=a.texture_sh, T=int(m["triangles"].shape[0]))) + "\n")
+            print("%s.shtex.npy, .shtex.json: %d SH coefficients per channel and texel (L = %d); the .png holds the view-independent part"
+                  % (stem, a.texture_sh ** 2, a.texture_sh))
     if compare:
         full = extract_surface(model, normals=False, colors=True, **kw) if a.simplify > 0 else m
-        for name, mesh, tex in (("textured mesh", m, True), ("vertex-coloured mesh", m, False), ("full-resolution vertex-coloured mesh", full, False)):
-            rep = render_check(model, mesh, a.render_check, textured=tex)[0]
+        renders = [("textured mesh", m, True, None), ("vertex-coloured mesh", m, False, None),
+                   ("full-resolution vertex-coloured mesh", full, False, None)]
+        if a.texture_sh > 0:  # the first line stays the flat atlas, baked for the check; the fourth is the SH atlas
+            flat = bake_texture(model, m["vertices"], m["triangles"], a.texture, normals=m["normals"])["texture"]
+            renders[0] = ("textured mesh", m, True, flat)
+            renders.append(("SH-textured mesh (L = %d)" % a.texture_sh, m, True, m["texture"]))
+        for name, mesh, tex, atlas in renders:
+            rep = render_check(model, mesh, a.render_check, textured=tex, texture=atlas)[0]
             print("render check, %d views at 200 x 200, %s (%d triangles) against the model's volume render: PSNR %.2f dB, SSIM %.4f"
                   % (a.render_check, name, mesh["triangles"].shape[0], rep["psnr"], rep["ssim"]))
     elif a.render_check > 0:
