@@ -1,6 +1,6 @@
 // mesh_expose.hip -- which triangles an outside view can see (csrc/pvd_hip_mesh_expose.h): an any-hit query from S points of every
-// triangle along D directions, over the workspace pvd_mesh_ray_build leaves (csrc/mesh_ray.hip) and with the walk and the watertight
-// test of csrc/mesh_ray_walk.h, which the first-hit cast uses too.
+// triangle along D directions, over the workspace pvd_mesh_ray_build leaves (csrc/mesh_ray.hip, csrc/mesh_tri_grid.h) and with the
+// walk and the watertight test of csrc/mesh_ray_walk.h, which the first-hit cast uses too.
 //
 // k_mx_expose    one wave per triangle, kWaves triangles per workgroup; lanes are directions, 64 at a time, in a loop over the points
 //                and the chunks of directions.  The sample point and the side test are in unfused float64; a lane walks until its
@@ -17,6 +17,7 @@
 namespace {
 
 using namespace pvd;
+using namespace pvd::tgrid;
 using namespace pvd::mray;
 
 struct AnyHit {  // the walk's visitor: is some valid triangle other than `self` hit with 0 <= t < +inf
@@ -114,12 +115,12 @@ extern "C" {
 int pvd_mesh_expose(const float *dirs, uint32_t D, uint32_t S, uint32_t tri0, uint32_t tri1, uint32_t T, uint32_t G, uint64_t pairs,
                     const void *workspace, size_t workspace_bytes, int32_t *counts, uint64_t *totals, pvd_stream_t stream) {
     if (D < 1 || D > PVD_MESH_EXPOSE_MAX_D || (S != 1 && S != 4)) return PVD_ERR_UNSUPPORTED;
-    const int rc = check_args(T, G, pairs, workspace, workspace_bytes);
+    const int rc = check_args<3>(T, G, pairs, workspace, workspace_bytes);
     if (rc != PVD_OK) return rc;
     if (!(tri0 <= tri1 && tri1 <= T)) return PVD_ERR_INVALID;
     if (tri0 == tri1) return PVD_OK;
     if (!dirs || !counts || !totals) return PVD_ERR_INVALID;
-    const Layout l = layout(T, G, pairs);
+    const Layout l = layout<3>(T, G, pairs);
     const char *ws = (const char *)workspace;
     hipLaunchKernelGGL(k_mx_expose, dim3(div_up(tri1 - tri0, kWaves)), dim3(kThreads), 0, (hipStream_t)stream, dirs, D, S, tri0, tri1, T, G,
                        (uint32_t)pairs, (const uint32_t *)ws, (const uint32_t *)(ws + l.start), (const uint32_t *)(ws + l.pairs),

@@ -1,77 +1,22 @@
 // mesh_ray_walk.h -- what the first-hit cast (csrc/mesh_ray.hip) and the any-hit exposure query (csrc/mesh_expose.hip) share: the
-// layout of the workspace pvd_mesh_ray_build leaves, the box, the ray's constants, steps 3 .. 7 of the watertight test in unfused
-// float64 and the walk over the grid (include/pvd_hip_mesh_ray.h: "Walk").  The two differ in what they do with a triangle that is
-// not missed and in when they stop; the walk takes that as a visitor:
+// ray's constants, steps 3 .. 7 of the watertight test in unfused float64 and the walk over the grid (include/pvd_hip_mesh_ray.h:
+// "Walk").  The layout of the workspace pvd_mesh_ray_build leaves and the box are those of csrc/mesh_tri_grid.h, three axes.
+// The two differ in what they do with a triangle that is not missed and in when they stop; the walk takes that as a visitor:
 //     void test(const float4 *packed, uint32_t j)   record j against the ray
 //     bool found() const                            nothing more needs testing (the any-hit query: a hit is held; the cast: never)
 //     bool settled(double t_exit) const             the walk may stop before the cell behind t_exit
 // Everything is defined here (the library is built without relocatable device code): each translation unit gets its own copy.
 #pragma once
 
-#include "mesh_grid.h"
-
-#include "../../include/pvd_hip_mesh_ray.h"
+#include "mesh_tri_grid.h"
 
 namespace pvd {
 namespace mray {
 
-constexpr uint32_t kMaxT = 0x7fffffffu;
-constexpr uint64_t kMaxPairs = 0x7fffffffull;
+using Box = tgrid::Box<3>;  // the grid of pvd_mesh_ray_build: csrc/mesh_tri_grid.h with three binned axes
 
-// header words (uint32): 0 = outside triangles (the list's cursor), 1..3 = bmin, 4..6 = bmax (float bits), 7 = pairs; 64 bytes in all
-constexpr size_t kHeaderBytes = 64;
-constexpr size_t kCellsPerSum = 256;  // cells per partial sum of the build's scan: block_scan.h's kThreads
-
-struct Layout {  // byte offsets into the workspace; the 16-byte records first, so that a 16-byte aligned workspace aligns them
-    size_t packed, start, cursor, bsum, outside, pairs, total;
-};
-
-inline Layout layout(uint32_t T, uint32_t G, uint64_t pairs) {
-    const size_t C = (size_t)G * G * G, NB = (C + kCellsPerSum - 1) / kCellsPerSum;
-    Layout l;
-    l.packed = kHeaderBytes;
-    l.start = l.packed + 48 * (size_t)T;
-    l.cursor = l.start + 4 * (C + 1);
-    l.bsum = l.cursor + 4 * C;
-    l.outside = l.bsum + 4 * NB;
-    l.pairs = l.outside + 4 * (size_t)T;
-    l.total = l.pairs + 4 * (size_t)pairs;
-    return l;
-}
-
-inline bool in_range(uint32_t T, uint32_t G, uint64_t pairs) { return G >= 1 && G <= PVD_MESH_RAY_MAX_G && T <= kMaxT && pairs <= kMaxPairs; }
-
-inline int check_args(uint32_t T, uint32_t G, uint64_t pairs, const void *workspace, size_t workspace_bytes) {
-    if (!workspace || ((uintptr_t)workspace & 15u)) return PVD_ERR_INVALID;
-    if (!in_range(T, G, pairs)) return PVD_ERR_UNSUPPORTED;
-    if (workspace_bytes < layout(T, G, pairs).total) return PVD_ERR_INVALID;
-    return PVD_OK;
-}
-
-// the pure parts (box, ranges, the test, the walk) are PVD_HD, __host__ __device__: a CPU build can walk the same code
+// the pure parts (the test, the walk) are PVD_HD, __host__ __device__: a CPU build can walk the same code
 PVD_HD float sel3(float x, float y, float z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
-
-struct Box {  // per axis: flat (one layer from -inf to +inf), the bounds, the cell size and its inverse, the dilation eps
-    bool flat[3];
-    double lo[3], hi[3], h[3], inv_h[3], eps[3];
-};
-
-PVD_HD Box box_of(const float *__restrict__ bmin3, const float *__restrict__ bmax3, uint32_t G) {
-    Box b;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double lo = (double)bmin3[a], hi = (double)bmax3[a];
-        const double ext = hi - lo;
-        const bool ok = ext > 0.0 && ext < (double)INFINITY;  // false for NaN
-        b.flat[a] = !ok;
-        b.lo[a] = ok ? lo : 0.0;
-        b.hi[a] = ok ? hi : 0.0;
-        b.h[a] = ok ? ext / (double)G : 0.0;
-        b.inv_h[a] = ok ? (double)G / ext : 0.0;
-        b.eps[a] = ok ? 0x1p-20 * ext : 0.0;
-    }
-    return b;
-}
 
 // ------------------------------------------------------------------------------------------- the watertight test, in float64
 struct Ray {  // the ray's constants, once per lane: the permuted origin, the shear, the permutation
@@ -134,7 +79,7 @@ template <typename Visitor>
 PVD_HD void walk(const double o[3], const double d[3], uint32_t T, uint32_t G, const uint32_t *__restrict__ header,
                  const uint32_t *__restrict__ start, const uint32_t *__restrict__ list, const uint32_t *__restrict__ outside,
                  const float4 *__restrict__ packed, uint32_t pairs, double t_min, double t_max, Visitor &vis) {
-    const Box box = box_of((const float *)(header + 1), (const float *)(header + 4), G);
+    const Box box = tgrid::box_of<3>((const float *)(header + 1), (const float *)(header + 4), G);
     // every index below is clamped: a damaged workspace stays inside itself
     const uint32_t n_pairs = umin(header[7], pairs), n_out = umin(header[0], T);
     // (1) clip to the dilated slabs

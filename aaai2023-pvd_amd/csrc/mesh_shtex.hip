@@ -8,26 +8,24 @@
 // k_st_project<L>  one lane per texel: the K x 3 accumulators stay in registers through the J directions of the batch; rgb[j] is read
 //                  as one 12-byte load per lane along M, the K entries of P's column are wave-uniform.  The lane then stores its own
 //                  K * 12 contiguous bytes (and loads them first where the batch is not the first).
-// k_st_sample<L>   ONE LANE PER RAY, as k_mt_sample: the lane evaluates the basis of its direction once (K registers) and folds each of
-//                  its four texels, K * 12 contiguous bytes (192 at L = 4, moved as wide loads), into three numbers as they arrive.
+// k_st_sample<L>   ONE LANE PER RAY, as k_mt_sample (the four texels and the bilinear mix: csrc/mesh_atlas.h, shared with it): the lane
+//                  evaluates the basis of its direction once (K registers) and folds each of its four texels, K * 12 contiguous
+//                  bytes (192 at L = 4, moved as wide loads), into three numbers as they arrive.
 //                  Several lanes per ray would put the K-term sums, which the header orders, across lanes and buy nothing that
 //                  neighbouring rays of a wave -- which hit the same and neighbouring cells -- do not already share in the cache;
 //                  profiles/mesh_shtex.txt has the measured time next to a copy of the bytes the hits touch.
 // No LDS, no atomics.  Every float operation is a single float32 one in the order of the header; nothing is fused (the build's
 // -ffp-contract=off, and the pragma below for a build without it).
-#include "mesh_grid.h"
+#include "mesh_atlas.h"
 
 #include "pvd_hip_mesh_shtex.h"
 
 namespace {
 
 using namespace pvd;
+using namespace pvd::atlas;
 
 constexpr int kThreads = 256;
-
-struct __attribute__((packed, aligned(4))) F3 {  // three floats moved as one 12-byte access
-    float x, y, z;
-};
 
 template <int L>
 struct __attribute__((packed, aligned(4))) Texel {  // the K x 3 floats of a texel, moved as wide accesses
@@ -124,16 +122,6 @@ __global__ __launch_bounds__(kThreads) void k_st_project(const F3 *__restrict__ 
     coef[t] = acc;
 }
 
-// fu, i0, tx of include/pvd_hip_mesh_tex.h from one weight (as in mesh_tex.hip)
-__device__ __forceinline__ void texel_of(float w, uint32_t mi, uint32_t &i0, float &t) {
-#pragma clang fp contract(off)
-    const float m = (float)mi;
-    const float fu = fminf(fmaxf(w * m, 0.0f), m);  // fmaxf(NaN, 0) = 0
-    const int fl = (int)floorf(fu);                 // 0 .. m
-    i0 = (uint32_t)(fl < (int)mi ? fl : (int)mi);
-    t = fu - (float)i0;
-}
-
 // the K-term sum of one texel and channel, k ascending
 template <int L>
 __device__ __forceinline__ F3 fold(const Texel<L> &c, const float (&Y)[L * L]) {
@@ -162,24 +150,13 @@ __global__ __launch_bounds__(kThreads) void k_st_sample(const Texel<L> *__restri
     F3 out = {bg3[0], bg3[1], bg3[2]};
     if (f >= 0 && (uint32_t)f < T) {
         const float beta = bary[2 * (size_t)r], gamma = bary[2 * (size_t)r + 1];
-        uint32_t i0, j0;
-        float tx, ty;
-        texel_of(beta, S - 3, i0, tx);
-        texel_of(gamma, S - 3, j0, ty);
-        const uint32_t k = (uint32_t)f >> 1, cy = k / C, cx = k - cy * C;
-        const bool odd = (f & 1) != 0;
-        // 0 <= i0, j0 <= S - 3: the four texels have 0 <= p, q <= S - 2 and stay inside the cell (cx, cy), so inside [Ht, Wt]
-        const uint32_t xa = cx * S + (odd ? S - 1 - i0 : i0), xb = cx * S + (odd ? S - 2 - i0 : i0 + 1);
-        const uint32_t ya = cy * S + (odd ? S - 1 - j0 : j0), yb = cy * S + (odd ? S - 2 - j0 : j0 + 1);
+        const Footprint p = footprint_of((uint32_t)f, beta, gamma, S, C);
         const F3 d = dirs[r];
         float Y[L * L];
         sh_basis<L>(d.x, d.y, d.z, Y);
-        const F3 c00 = fold<L>(texture[(size_t)ya * Wt + xa], Y), c10 = fold<L>(texture[(size_t)ya * Wt + xb], Y);
-        const F3 c01 = fold<L>(texture[(size_t)yb * Wt + xa], Y), c11 = fold<L>(texture[(size_t)yb * Wt + xb], Y);
-        const float sx = 1.0f - tx, sy = 1.0f - ty;
-        out.x = unit_clamp((c00.x * sx + c10.x * tx) * sy + (c01.x * sx + c11.x * tx) * ty);
-        out.y = unit_clamp((c00.y * sx + c10.y * tx) * sy + (c01.y * sx + c11.y * tx) * ty);
-        out.z = unit_clamp((c00.z * sx + c10.z * tx) * sy + (c01.z * sx + c11.z * tx) * ty);
+        out = blend(fold<L>(texture[(size_t)p.ya * Wt + p.xa], Y), fold<L>(texture[(size_t)p.ya * Wt + p.xb], Y),
+                    fold<L>(texture[(size_t)p.yb * Wt + p.xa], Y), fold<L>(texture[(size_t)p.yb * Wt + p.xb], Y), p);
+        out = {unit_clamp(out.x), unit_clamp(out.y), unit_clamp(out.z)};
     }
     color[r] = out;
 }

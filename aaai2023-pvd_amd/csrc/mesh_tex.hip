@@ -4,16 +4,18 @@
 // k_mt_points    one lane per texel of a band of image rows, consecutive lanes along x (blockIdx.y is the row): the owner from integer
 //                arithmetic, its three indices and corners (the lanes of a cell share them: one cache line per wave and corner), the
 //                weights, six floats out as two 12-byte stores.  A pure store stream of 24 B per texel.  No LDS, no atomics.
-// k_mt_sample    one lane per ray: four 12-byte gathers out of the triangle's own cell, the bilinear mix.  No LDS, no atomics.
+// k_mt_sample    one lane per ray: four 12-byte gathers out of the triangle's own cell (their addresses and the bilinear mix:
+//                csrc/mesh_atlas.h, shared with csrc/mesh_shtex.hip).  No LDS, no atomics.
 // Every float operation is a single float32 one in the order of the header; nothing is fused (the build's -ffp-contract=off, and the
 // pragma below for a build without it).
-#include "mesh_grid.h"
+#include "mesh_atlas.h"
 
 #include "../../include/pvd_hip_mesh_tex.h"
 
 namespace {
 
 using namespace pvd;
+using namespace pvd::atlas;
 
 constexpr int kThreads = 256;
 
@@ -44,10 +46,6 @@ int layout_of(uint32_t T, uint32_t S, TexLayout &l) {
     l.Ht = (uint32_t)(rows * S);
     return PVD_OK;
 }
-
-struct __attribute__((packed, aligned(4))) F3 {  // three floats moved as one 12-byte access
-    float x, y, z;
-};
 
 PVD_HD float mix3(float wa, float wb, float wc, float a, float b, float c) {
 #pragma clang fp contract(off)
@@ -102,16 +100,6 @@ __global__ __launch_bounds__(kThreads) void k_mt_points(const float *__restrict_
     out_n[e] = N;
 }
 
-// fu, i0, tx of the header from one weight
-__device__ __forceinline__ void texel_of(float w, uint32_t mi, uint32_t &i0, float &t) {
-#pragma clang fp contract(off)
-    const float m = (float)mi;
-    const float fu = fminf(fmaxf(w * m, 0.0f), m);  // fmaxf(NaN, 0) = 0
-    const int fl = (int)floorf(fu);                 // 0 .. m
-    i0 = (uint32_t)(fl < (int)mi ? fl : (int)mi);
-    t = fu - (float)i0;
-}
-
 __global__ __launch_bounds__(kThreads) void k_mt_sample(const F3 *__restrict__ texture, uint32_t T, uint32_t S, uint32_t C, uint32_t Wt,
                                                        const int32_t *__restrict__ tri, const float *__restrict__ bary, uint32_t N,
                                                        const float *__restrict__ bg3, F3 *__restrict__ color) {
@@ -122,21 +110,9 @@ __global__ __launch_bounds__(kThreads) void k_mt_sample(const F3 *__restrict__ t
     F3 out = {bg3[0], bg3[1], bg3[2]};
     if (f >= 0 && (uint32_t)f < T) {
         const float beta = bary[2 * (size_t)r], gamma = bary[2 * (size_t)r + 1];
-        uint32_t i0, j0;
-        float tx, ty;
-        texel_of(beta, S - 3, i0, tx);
-        texel_of(gamma, S - 3, j0, ty);
-        const uint32_t k = (uint32_t)f >> 1, cy = k / C, cx = k - cy * C;
-        const bool odd = (f & 1) != 0;
-        // 0 <= i0, j0 <= S - 3: the four texels have 0 <= p, q <= S - 2 and stay inside the cell (cx, cy)
-        const uint32_t xa = cx * S + (odd ? S - 1 - i0 : i0), xb = cx * S + (odd ? S - 2 - i0 : i0 + 1);
-        const uint32_t ya = cy * S + (odd ? S - 1 - j0 : j0), yb = cy * S + (odd ? S - 2 - j0 : j0 + 1);
-        const F3 c00 = texture[(size_t)ya * Wt + xa], c10 = texture[(size_t)ya * Wt + xb];
-        const F3 c01 = texture[(size_t)yb * Wt + xa], c11 = texture[(size_t)yb * Wt + xb];
-        const float sx = 1.0f - tx, sy = 1.0f - ty;
-        out.x = (c00.x * sx + c10.x * tx) * sy + (c01.x * sx + c11.x * tx) * ty;
-        out.y = (c00.y * sx + c10.y * tx) * sy + (c01.y * sx + c11.y * tx) * ty;
-        out.z = (c00.z * sx + c10.z * tx) * sy + (c01.z * sx + c11.z * tx) * ty;
+        const Footprint p = footprint_of((uint32_t)f, beta, gamma, S, C);
+        out = blend(texture[(size_t)p.ya * Wt + p.xa], texture[(size_t)p.ya * Wt + p.xb], texture[(size_t)p.yb * Wt + p.xa],
+                    texture[(size_t)p.yb * Wt + p.xb], p);
     }
     color[r] = out;
 }

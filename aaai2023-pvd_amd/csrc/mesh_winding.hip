@@ -1,13 +1,8 @@
 // mesh_winding.hip -- the integer winding number of points, and of every point of an R^3 lattice, against a triangle mesh
 // (include/pvd_hip_mesh_winding.h): signed crossings of the ray along +z, in unfused float64, over a two-dimensional grid of the
-// triangles' dilated bounding boxes in x and y, built on the device as csrc/mesh_ray.hip builds its three-dimensional one.
+// triangles' dilated bounding boxes in x and y, built on the device (csrc/mesh_tri_grid.h, two binned axes: k_tg_count<2>,
+// k_tg_bin<2>, the scan of csrc/block_scan.h, k_tg_fill<2>; the record carries the directions of the triangle's three edges).
 //
-// k_mw_count     one lane per triangle: validity, inside / outside, the number of cells of its range; one integer atomicAdd per
-//                wave on each of the two 64-bit totals.
-// k_mw_bin       one lane per triangle: the packed record (index -1: invalid; the directions of its three edges), one integer
-//                atomicAdd per cell of its range on the cell's count, or a slot of the outside list.
-// k_blocksum, k_scan, k_offsets   (csrc/block_scan.h) the per-cell counts -> the cell starts and fill cursors.
-// k_mw_fill      one lane per triangle: per cell of its range a slot from the cell's cursor (integer atomicAdd), its index into it.
 // k_mw_points    one lane per point: the cell's list, then the outside list.  No LDS, no atomics.
 // k_mw_lattice   one wave per column (i, j), kColsPerWave columns after one another: the lanes share out the column's triangles,
 //                every crossing adds its sign into the column's difference array in LDS (integer LDS atomics), the wave takes the
@@ -15,159 +10,15 @@
 //                The four totals: registers -> one workgroup sum -> at most four integer atomics per workgroup.
 // No workgroup waits on another one of the same launch, and no loop retries an atomic.  The order of the pairs inside a cell depends
 // on the run; a sum of integers does not.
-#include "block_scan.h"
-#include "mesh_grid.h"
-
-#include "../../include/pvd_hip_mesh_winding.h"
+#include "mesh_tri_grid.h"
 
 namespace {
 
 using namespace pvd;
+using namespace pvd::tgrid;  // the workspace's layout and its build
 
-constexpr uint32_t kMaxT = 0x7fffffffu;
-constexpr uint64_t kMaxPairs = 0x7fffffffull;
 constexpr int kMaxR = PVD_MESH_WINDING_MAX_R;
 constexpr int kColsPerWave = 4;  // columns a wave of k_mw_lattice walks: neighbours in j, so mostly one cell's list, still warm
-
-// header words (uint32): 0 = outside triangles (the list's cursor), 1..3 = bmin, 4..6 = bmax (float bits), 7 = pairs; 64 bytes in all
-constexpr size_t kHeaderBytes = 64;
-
-struct Layout {  // byte offsets into the workspace; the 16-byte records first, so that a 16-byte aligned workspace aligns them
-    size_t packed, start, cursor, bsum, outside, pairs, total;
-};
-
-inline Layout layout(uint32_t T, uint32_t G, uint64_t pairs) {
-    const size_t C = (size_t)G * G, NB = (C + kThreads - 1) / kThreads;
-    Layout l;
-    l.packed = kHeaderBytes;
-    l.start = l.packed + 48 * (size_t)T;
-    l.cursor = l.start + 4 * (C + 1);
-    l.bsum = l.cursor + 4 * C;
-    l.outside = l.bsum + 4 * NB;
-    l.pairs = l.outside + 4 * (size_t)T;
-    l.total = l.pairs + 4 * (size_t)pairs;
-    return l;
-}
-
-struct Box {  // x and y only; per axis: flat (one layer from -inf to +inf), the bounds, the inverse cell size, the dilation eps
-    bool flat[2];
-    double lo[2], hi[2], inv_h[2], eps[2];
-};
-
-PVD_HD Box box_of(const float *__restrict__ bmin3, const float *__restrict__ bmax3, uint32_t G) {
-    Box b;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const double lo = (double)bmin3[a], hi = (double)bmax3[a];
-        const double ext = hi - lo;
-        const bool ok = ext > 0.0 && ext < (double)INFINITY;  // false for NaN
-        b.flat[a] = !ok;
-        b.lo[a] = ok ? lo : 0.0;
-        b.hi[a] = ok ? hi : 0.0;
-        b.inv_h[a] = ok ? (double)G / ext : 0.0;
-        b.eps[a] = ok ? 0x1p-20 * ext : 0.0;
-    }
-    return b;
-}
-
-enum : int { kInvalid = 0, kInside = 1, kOutside = 2 };
-
-// the class of triangle t, for an inside one its range of cells k0 .. k1 per axis, and the directions of its edges: bit 0 = (b, c)
-// runs from the lower to the higher index, bit 1 = (c, a), bit 2 = (a, b)
-PVD_HD int classify(const float *__restrict__ vertices, uint32_t V, const int32_t *__restrict__ triangles, uint32_t t, const Box &box,
-                    uint32_t G, int k0[2], int k1[2], float corners[9], uint32_t &dirs) {
-    const int32_t ia = triangles[3 * (size_t)t], ib = triangles[3 * (size_t)t + 1], ic = triangles[3 * (size_t)t + 2];
-    if (!((uint32_t)ia < V && (uint32_t)ib < V && (uint32_t)ic < V)) return kInvalid;  // a negative index is a large unsigned one
-    dirs = (ib < ic ? 1u : 0u) | (ic < ia ? 2u : 0u) | (ia < ib ? 4u : 0u);
-    const float *pa = vertices + 3 * (size_t)ia, *pb = vertices + 3 * (size_t)ib, *pc = vertices + 3 * (size_t)ic;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        corners[q] = pa[q];
-        corners[3 + q] = pb[q];
-        corners[6 + q] = pc[q];
-    }
-    if (!(finite3(corners[0], corners[1], corners[2]) && finite3(corners[3], corners[4], corners[5]) &&
-          finite3(corners[6], corners[7], corners[8])))
-        return kInvalid;
-    bool inside = true;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const double mn = (double)fminf(corners[a], fminf(corners[3 + a], corners[6 + a]));
-        const double mx = (double)fmaxf(corners[a], fmaxf(corners[3 + a], corners[6 + a]));
-        if (!box.flat[a] && !(box.lo[a] <= mn && mx <= box.hi[a])) inside = false;
-        k0[a] = cell_axis(box, a, mn - box.eps[a], G);
-        k1[a] = cell_axis(box, a, mx + box.eps[a], G);
-    }
-    return inside ? kInside : kOutside;
-}
-
-// a triangle's range holds at most 2^20 cells and a wave 64 triangles: the wave's sum fits 32 bits, the totals are 64 bits wide
-__global__ __launch_bounds__(kThreads) void k_mw_count(const float *__restrict__ vertices, uint32_t V, const int32_t *__restrict__ triangles,
-                                                      uint32_t T, const float *__restrict__ bmin3, const float *__restrict__ bmax3, uint32_t G,
-                                                      unsigned long long *__restrict__ totals) {
-    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
-    uint32_t cells = 0, out = 0;
-    if (t < T) {
-        int k0[2], k1[2];
-        float c[9];
-        uint32_t dirs;
-        const int cls = classify(vertices, V, triangles, t, box_of(bmin3, bmax3, G), G, k0, k1, c, dirs);
-        if (cls == kInside) cells = (uint32_t)(k1[0] - k0[0] + 1) * (uint32_t)(k1[1] - k0[1] + 1);
-        out = cls == kOutside ? 1u : 0u;
-    }
-    cells = wave_sum(cells);
-    out = wave_sum(out);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        if (cells) atomicAdd(&totals[0], (unsigned long long)cells);
-        if (out) atomicAdd(&totals[1], (unsigned long long)out);
-    }
-}
-
-// the grid has at least one workgroup, so that the box reaches the header when T == 0 too
-__global__ __launch_bounds__(kThreads) void k_mw_bin(const float *__restrict__ vertices, uint32_t V, const int32_t *__restrict__ triangles,
-                                                    uint32_t T, const float *__restrict__ bmin3, const float *__restrict__ bmax3, uint32_t G,
-                                                    uint32_t *__restrict__ header, uint32_t *__restrict__ cursor,
-                                                    uint32_t *__restrict__ outside, float4 *__restrict__ packed) {
-    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
-    if (t < 3) {
-        header[1 + t] = f2u(bmin3[t]);
-        header[4 + t] = f2u(bmax3[t]);
-    }
-    if (t >= T) return;
-    int k0[2], k1[2];
-    float c[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    uint32_t dirs = 0;
-    const int cls = classify(vertices, V, triangles, t, box_of(bmin3, bmax3, G), G, k0, k1, c, dirs);
-    float4 *o = packed + 3 * (size_t)t;
-    o[0] = make_float4(c[0], c[1], c[2], c[3]);
-    o[1] = make_float4(c[4], c[5], c[6], c[7]);
-    o[2] = make_float4(c[8], u2f(cls == kInvalid ? 0xffffffffu : t), u2f(dirs), 0.0f);
-    if (cls == kInside) {
-        for (int x = k0[0]; x <= k1[0]; ++x)
-            for (int y = k0[1]; y <= k1[1]; ++y) atomicAdd(&cursor[(uint32_t)x * G + (uint32_t)y], 1u);
-    } else if (cls == kOutside) {
-        const uint32_t slot = atomicAdd(&header[0], 1u);
-        if (slot < T) outside[slot] = t;  // (always: at most T triangles are outside)
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_mw_fill(const float *__restrict__ vertices, uint32_t V, const int32_t *__restrict__ triangles,
-                                                     uint32_t T, const uint32_t *__restrict__ header, uint32_t G, uint32_t pairs,
-                                                     uint32_t *__restrict__ cursor, uint32_t *__restrict__ list) {
-    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
-    if (t >= T) return;
-    int k0[2], k1[2];
-    float c[9];
-    uint32_t dirs;
-    // the same box, bit for bit, as k_mw_bin read: the ranges agree with the counts
-    if (classify(vertices, V, triangles, t, box_of((const float *)(header + 1), (const float *)(header + 4), G), G, k0, k1, c, dirs) != kInside)
-        return;
-    for (int x = k0[0]; x <= k1[0]; ++x)
-        for (int y = k0[1]; y <= k1[1]; ++y) {
-            const uint32_t slot = atomicAdd(&cursor[(uint32_t)x * G + (uint32_t)y], 1u);
-            if (slot < pairs) list[slot] = t;  // a `pairs` below the true total loses pairs and stays inside the workspace
-        }
-}
 
 // ------------------------------------------------------------------------------------------ one triangle against one column
 // the directed edge function of u -> w at (px, py), evaluated from the lower to the higher index (`up`: u is the lower one) and
@@ -216,7 +67,7 @@ struct Column {
 
 PVD_HD Column column_of(double px, double py, uint32_t T, uint32_t G, uint32_t pairs, const uint32_t *__restrict__ header,
                         const uint32_t *__restrict__ start) {
-    const Box box = box_of((const float *)(header + 1), (const float *)(header + 4), G);
+    const Box<2> box = box_of<2>((const float *)(header + 1), (const float *)(header + 4), G);
     const uint32_t n_pairs = umin(header[7], pairs);
     Column c;
     c.n_out = umin(header[0], T);
@@ -354,68 +205,34 @@ __global__ __launch_bounds__(kThreads) void k_mw_lattice(uint32_t R, const float
     }
 }
 
-bool in_range(uint32_t T, uint32_t G, uint64_t pairs) { return G >= 1 && G <= PVD_MESH_WINDING_MAX_G && T <= kMaxT && pairs <= kMaxPairs; }
-
-int check_args(uint32_t T, uint32_t G, uint64_t pairs, const void *workspace, size_t workspace_bytes) {
-    if (!workspace || ((uintptr_t)workspace & 15u)) return PVD_ERR_INVALID;
-    if (!in_range(T, G, pairs)) return PVD_ERR_UNSUPPORTED;
-    if (workspace_bytes < layout(T, G, pairs).total) return PVD_ERR_INVALID;
-    return PVD_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-size_t pvd_mesh_winding_workspace_bytes(uint32_t T, uint32_t G, uint64_t pairs) { return in_range(T, G, pairs) ? layout(T, G, pairs).total : 0; }
+size_t pvd_mesh_winding_workspace_bytes(uint32_t T, uint32_t G, uint64_t pairs) { return in_range<2>(T, G, pairs) ? layout<2>(T, G, pairs).total : 0; }
 
 int pvd_mesh_winding_count(const float *vertices, uint32_t V, const int32_t *triangles, uint32_t T, const float *bmin3, const float *bmax3,
                            uint32_t G, uint64_t *totals, pvd_stream_t stream) {
     if (!bmin3 || !bmax3 || !totals || (T && !triangles) || (T && V && !vertices)) return PVD_ERR_INVALID;
-    if (!in_range(T, G, 0)) return PVD_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if ((rc = check_memset(hipMemsetAsync(totals, 0, 16, st))) != PVD_OK) return rc;
-    if (T == 0) return PVD_OK;
-    hipLaunchKernelGGL(k_mw_count, dim3(div_up(T, kThreads)), dim3(kThreads), 0, st, vertices, V, triangles, T, bmin3, bmax3, G,
-                       (unsigned long long *)totals);
-    return check_launch();
+    if (!in_range<2>(T, G, 0)) return PVD_ERR_UNSUPPORTED;
+    return count<2>(vertices, V, triangles, T, bmin3, bmax3, G, totals, (hipStream_t)stream);
 }
 
 int pvd_mesh_winding_build(const float *vertices, uint32_t V, const int32_t *triangles, uint32_t T, const float *bmin3, const float *bmax3,
                            uint32_t G, uint64_t pairs, void *workspace, size_t workspace_bytes, pvd_stream_t stream) {
     if (!bmin3 || !bmax3 || (T && !triangles) || (T && V && !vertices)) return PVD_ERR_INVALID;
-    int rc = check_args(T, G, pairs, workspace, workspace_bytes);
+    const int rc = check_args<2>(T, G, pairs, workspace, workspace_bytes);
     if (rc != PVD_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const Layout l = layout(T, G, pairs);
-    const uint32_t C = G * G, NB = div_up(C, kThreads), TB = T ? div_up(T, kThreads) : 1u;
-    char *ws = (char *)workspace;
-    uint32_t *header = (uint32_t *)ws, *start = (uint32_t *)(ws + l.start), *cursor = (uint32_t *)(ws + l.cursor);
-    uint32_t *bsum = (uint32_t *)(ws + l.bsum), *outside = (uint32_t *)(ws + l.outside), *list = (uint32_t *)(ws + l.pairs);
-    float4 *packed = (float4 *)(ws + l.packed);
-    if ((rc = check_memset(hipMemsetAsync(header, 0, kHeaderBytes, st))) != PVD_OK) return rc;
-    if ((rc = check_memset(hipMemsetAsync(cursor, 0, 4 * (size_t)C, st))) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_mw_bin, dim3(TB), dim3(kThreads), 0, st, vertices, V, triangles, T, bmin3, bmax3, G, header, cursor, outside, packed);
-    if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_blocksum<uint32_t>, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum);
-    if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_scan<uint32_t>, dim3(1), dim3(kScanThreads), 0, st, bsum, NB, start + C, header + 7);
-    if ((rc = check_launch()) != PVD_OK) return rc;
-    hipLaunchKernelGGL(k_offsets<uint32_t>, dim3(NB), dim3(kThreads), 0, st, cursor, C, bsum, start);
-    if ((rc = check_launch()) != PVD_OK) return rc;
-    if (T == 0) return PVD_OK;
-    hipLaunchKernelGGL(k_mw_fill, dim3(TB), dim3(kThreads), 0, st, vertices, V, triangles, T, header, G, (uint32_t)pairs, cursor, list);
-    return check_launch();
+    return build<2>(vertices, V, triangles, T, bmin3, bmax3, G, pairs, workspace, (hipStream_t)stream);
 }
 
 int pvd_mesh_winding_points(const float *points, uint32_t N, uint32_t T, uint32_t G, uint64_t pairs, const void *workspace,
                             size_t workspace_bytes, int32_t *winding, pvd_stream_t stream) {
-    const int rc = check_args(T, G, pairs, workspace, workspace_bytes);
+    const int rc = check_args<2>(T, G, pairs, workspace, workspace_bytes);
     if (rc != PVD_OK) return rc;
     if (N == 0) return PVD_OK;
     if (!points || !winding) return PVD_ERR_INVALID;
-    const Layout l = layout(T, G, pairs);
+    const Layout l = layout<2>(T, G, pairs);
     const char *ws = (const char *)workspace;
     hipLaunchKernelGGL(k_mw_points, dim3(div_up(N, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, points, N, T, G, (uint32_t)pairs,
                        (const uint32_t *)ws, (const uint32_t *)(ws + l.start), (const uint32_t *)(ws + l.pairs),
@@ -426,12 +243,12 @@ int pvd_mesh_winding_points(const float *points, uint32_t N, uint32_t T, uint32_
 int pvd_mesh_winding_lattice(uint32_t R, const float *lat_bmin3, const float *lat_bmax3, uint32_t T, uint32_t G, uint64_t pairs,
                              const void *workspace, size_t workspace_bytes, int32_t *winding, int64_t *totals, pvd_stream_t stream) {
     if (!lat_bmin3 || !lat_bmax3 || !winding || !totals) return PVD_ERR_INVALID;
-    int rc = check_args(T, G, pairs, workspace, workspace_bytes);
+    int rc = check_args<2>(T, G, pairs, workspace, workspace_bytes);
     if (rc != PVD_OK) return rc;
     if (R < 2 || R > PVD_MESH_WINDING_MAX_R) return PVD_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = check_memset(hipMemsetAsync(totals, 0, 32, st))) != PVD_OK) return rc;
-    const Layout l = layout(T, G, pairs);
+    const Layout l = layout<2>(T, G, pairs);
     const char *ws = (const char *)workspace;
     hipLaunchKernelGGL(k_mw_lattice, dim3(div_up(R * R, kWaves * kColsPerWave)), dim3(kThreads), 0, st, R, lat_bmin3, lat_bmax3, T, G,
                        (uint32_t)pairs, (const uint32_t *)ws, (const uint32_t *)(ws + l.start), (const uint32_t *)(ws + l.pairs),

@@ -597,26 +597,32 @@ def face_vertex_normals(vertices, triangles):
     return torch.where(good, acc / torch.where(good, length, torch.ones_like(length)), torch.zeros_like(acc)).contiguous()
 
 
-def _ray_grid(vertices, triangles, bmin, bmax, grid):
-    """(T, G, pairs, workspace): the uniform grid of include/pvd_hip_mesh_ray.h over the mesh, as pvd_mesh_ray_cast and pvd_mesh_expose
-    read it.  One read-back: the two totals of the count pass."""
+def _tri_grid(api, vertices, triangles, bmin, bmax, grid):
+    """(T, G, pairs, workspace): the uniform grid of csrc/mesh_tri_grid.h over the mesh, as the queries of `api` read it -- "mesh_ray":
+    include/pvd_hip_mesh_ray.h, G^3 cells; "mesh_winding": include/pvd_hip_mesh_winding.h, G^2 cells over x and y.  One read-back: the
+    two totals of the count pass."""
     import pvd_hip
     dev = vertices.device
     vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
     triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
     T = int(triangles.shape[0])
-    G = default_grid(T) if grid is None else int(grid)  # (a grid outside 1 .. 256 is an error of the binding's, not clamped)
+    G = default_grid(T) if grid is None else int(grid)  # (a grid outside the binding's 1 .. MAX_G is its error, not clamped)
     lo, hi = _finite_box(vertices) if bmin is None or bmax is None else (None, None)
     if bmin is not None:
         lo = torch.as_tensor(bmin, dtype=torch.float32, device=dev).reshape(3).contiguous()
     if bmax is not None:
         hi = torch.as_tensor(bmax, dtype=torch.float32, device=dev).reshape(3).contiguous()
     totals = torch.zeros(2, dtype=torch.int64, device=dev)
-    pvd_hip.mesh_ray_count(vertices, triangles, lo, hi, G, totals)
+    getattr(pvd_hip, api + "_count")(vertices, triangles, lo, hi, G, totals)
     pairs = int(totals.tolist()[0])
-    ws = torch.empty(pvd_hip.mesh_ray_workspace_bytes(T, G, pairs), dtype=torch.uint8, device=dev)
-    pvd_hip.mesh_ray_build(vertices, triangles, lo, hi, G, pairs, ws)
+    ws = torch.empty(getattr(pvd_hip, api + "_workspace_bytes")(T, G, pairs), dtype=torch.uint8, device=dev)
+    getattr(pvd_hip, api + "_build")(vertices, triangles, lo, hi, G, pairs, ws)
     return T, G, pairs, ws
+
+
+def _ray_grid(vertices, triangles, bmin, bmax, grid):
+    """The grid pvd_mesh_ray_cast and pvd_mesh_expose read."""
+    return _tri_grid("mesh_ray", vertices, triangles, bmin, bmax, grid)
 
 
 def mesh_raycast(origins, dirs, vertices, triangles, t_min=0.0, t_max=float("inf"), bmin=None, bmax=None, grid=None):
@@ -837,26 +843,6 @@ def evaluate_mesh_views(vertices, triangles, colors, poses, intrinsics, H, W, tr
 
 
 # ------------------------------------------------------------------------------------------------ inside and outside: winding numbers
-def _winding_mesh(vertices, triangles, bmin, bmax, grid):
-    """The two-dimensional grid of include/pvd_hip_mesh_winding.h over the mesh: (T, G, pairs, workspace).  One read-back: the two
-    totals of the count pass."""
-    import pvd_hip
-    dev = vertices.device
-    T = int(triangles.shape[0])
-    G = default_grid(T) if grid is None else int(grid)  # (a grid outside 1 .. 1024 is an error of the binding's, not clamped)
-    lo, hi = _finite_box(vertices) if bmin is None or bmax is None else (None, None)
-    if bmin is not None:
-        lo = torch.as_tensor(bmin, dtype=torch.float32, device=dev).reshape(3).contiguous()
-    if bmax is not None:
-        hi = torch.as_tensor(bmax, dtype=torch.float32, device=dev).reshape(3).contiguous()
-    totals = torch.zeros(2, dtype=torch.int64, device=dev)
-    pvd_hip.mesh_winding_count(vertices, triangles, lo, hi, G, totals)
-    pairs = int(totals.tolist()[0])
-    ws = torch.empty(pvd_hip.mesh_winding_workspace_bytes(T, G, pairs), dtype=torch.uint8, device=dev)
-    pvd_hip.mesh_winding_build(vertices, triangles, lo, hi, G, pairs, ws)
-    return T, G, pairs, ws
-
-
 def mesh_winding(points, vertices, triangles, bmin=None, bmax=None, grid=None):
     """w [N] int32 on the device: the winding number of every row of points [N,3] about the mesh (vertices [V,3] f32, triangles [T,3]
     int32) -- the signed crossings of the ray along +z, in unfused float64 with a tie rule that counts a ray through a shared edge or
@@ -868,7 +854,7 @@ def mesh_winding(points, vertices, triangles, bmin=None, bmax=None, grid=None):
     points = points.to(torch.float32).reshape(-1, 3).contiguous()
     vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
     triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
-    T, G, pairs, ws = _winding_mesh(vertices, triangles, bmin, bmax, grid)
+    T, G, pairs, ws = _tri_grid("mesh_winding", vertices, triangles, bmin, bmax, grid)
     w = torch.empty(points.shape[0], dtype=torch.int32, device=vertices.device)
     pvd_hip.mesh_winding_points(points, T, G, pairs, ws, w)
     return w
@@ -893,7 +879,7 @@ def voxelize_mesh(vertices, triangles, R, bmin, bmax, grid=None, return_totals=F
     triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
     R = int(R)
     lo, hi = _box(bmin, bmax, dev)
-    T, G, pairs, ws = _winding_mesh(vertices, triangles, None, None, grid)
+    T, G, pairs, ws = _tri_grid("mesh_winding", vertices, triangles, None, None, grid)
     w = torch.empty(R, R, R, dtype=torch.int32, device=dev) if 2 <= R <= pvd_hip.MESH_WINDING_MAX_R else torch.empty(0, dtype=torch.int32, device=dev)
     totals = torch.zeros(4, dtype=torch.int64, device=dev)
     pvd_hip.mesh_winding_lattice(R, lo, hi, T, G, pairs, ws, w, totals)

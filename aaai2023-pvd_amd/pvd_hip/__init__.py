@@ -1877,43 +1877,56 @@ def mesh_simplify_emit(vertices, triangles, attrs, bmin, bmax, G, workspace, out
 MESH_RAY_MAX_G = 256  # PVD_MESH_RAY_MAX_G: cells per axis, 1 .. 256
 
 
-def mesh_ray_workspace_bytes(T, G, pairs):
-    """pvd_mesh_ray_workspace_bytes: bytes of workspace mesh_ray_build / mesh_ray_cast need for T triangles, G^3 cells and `pairs`
-    (cell, triangle) pairs (the first total of mesh_ray_count)."""
+# the triangle grid of csrc/mesh_tri_grid.h behind pvd_<prefix>_{workspace_bytes,count,build}: "mesh_ray" (G^3 cells) and "mesh_winding" (G^2)
+def _tri_grid_workspace_bytes(prefix, max_G, T, G, pairs):
+    name = "pvd_%s_workspace_bytes" % prefix
     ok = 0 <= int(T) < 2 ** 32 and 0 <= int(G) < 2 ** 32 and 0 <= int(pairs) < 2 ** 64
-    n = int(_lib.pvd_mesh_ray_workspace_bytes(_u32(T), _u32(G), _u64(pairs))) if ok else 0
+    n = int(getattr(_lib, name)(_u32(T), _u32(G), _u64(pairs))) if ok else 0
     if n == 0:
-        raise PvdHipError("pvd_mesh_ray_workspace_bytes: G must be 1 .. %d, T and pairs below 2^31, got T=%d G=%d pairs=%d"
-                          % (MESH_RAY_MAX_G, int(T), int(G), int(pairs)))
+        raise PvdHipError("%s: G must be 1 .. %d, T and pairs below 2^31, got T=%d G=%d pairs=%d" % (name, max_G, int(T), int(G), int(pairs)))
     return n
 
 
-def _mesh_ray_mesh(vertices, triangles, bmin, bmax, G):
+def _tri_grid_mesh(max_G, vertices, triangles, bmin, bmax, G):
     V, T = _mesh_and_box(vertices, triangles, bmin, bmax)
-    if not 1 <= int(G) <= MESH_RAY_MAX_G:
-        raise PvdHipError("G must be 1 .. %d, got %d" % (MESH_RAY_MAX_G, int(G)))
+    if not 1 <= int(G) <= max_G:
+        raise PvdHipError("G must be 1 .. %d, got %d" % (max_G, int(G)))
     return V, T
+
+
+def _tri_grid_count(prefix, max_G, vertices, triangles, bmin, bmax, G, totals):
+    dev = _dev(vertices, triangles, bmin, bmax, totals)
+    V, T = _tri_grid_mesh(max_G, vertices, triangles, bmin, bmax, G)
+    _want(totals, torch.int64, "totals")
+    if totals.numel() < 2:
+        raise PvdHipError("totals must hold 2 int64 values")
+    _call("pvd_%s_count" % prefix, dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _p(totals))
+
+
+def _tri_grid_build(prefix, max_G, vertices, triangles, bmin, bmax, G, pairs, workspace):
+    dev = _dev(vertices, triangles, bmin, bmax, workspace)
+    V, T = _tri_grid_mesh(max_G, vertices, triangles, bmin, bmax, G)
+    _mesh_workspace(workspace, _tri_grid_workspace_bytes(prefix, max_G, T, G, pairs), "%s_workspace_bytes(T, G, pairs)" % prefix)
+    _call("pvd_%s_build" % prefix, dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _u64(pairs),
+          _p(workspace), ctypes.c_size_t(workspace.numel()))
+
+
+def mesh_ray_workspace_bytes(T, G, pairs):
+    """pvd_mesh_ray_workspace_bytes: bytes of workspace mesh_ray_build / mesh_ray_cast need for T triangles, G^3 cells and `pairs`
+    (cell, triangle) pairs (the first total of mesh_ray_count)."""
+    return _tri_grid_workspace_bytes("mesh_ray", MESH_RAY_MAX_G, T, G, pairs)
 
 
 def mesh_ray_count(vertices, triangles, bmin, bmax, G, totals):
     """pvd_mesh_ray_count: totals int64 [2] on the device <- (the (cell, triangle) pairs, the outside triangles) of the mesh (vertices
     [V,3] f32, triangles [T,3] int32) over G^3 cells of the box bmin .. bmax (device f32 [3] each)."""
-    dev = _dev(vertices, triangles, bmin, bmax, totals)
-    V, T = _mesh_ray_mesh(vertices, triangles, bmin, bmax, G)
-    _want(totals, torch.int64, "totals")
-    if totals.numel() < 2:
-        raise PvdHipError("totals must hold 2 int64 values")
-    _call("pvd_mesh_ray_count", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _p(totals))
+    _tri_grid_count("mesh_ray", MESH_RAY_MAX_G, vertices, triangles, bmin, bmax, G, totals)
 
 
 def mesh_ray_build(vertices, triangles, bmin, bmax, G, pairs, workspace):
     """pvd_mesh_ray_build: bins the valid triangles of the SAME mesh, box and G as mesh_ray_count, with the `pairs` it left, and leaves
     in the workspace (uint8, mesh_ray_workspace_bytes(T, G, pairs)) what mesh_ray_cast needs."""
-    dev = _dev(vertices, triangles, bmin, bmax, workspace)
-    V, T = _mesh_ray_mesh(vertices, triangles, bmin, bmax, G)
-    _mesh_workspace(workspace, mesh_ray_workspace_bytes(T, G, pairs), "mesh_ray_workspace_bytes(T, G, pairs)")
-    _call("pvd_mesh_ray_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _u64(pairs), _p(workspace),
-          ctypes.c_size_t(workspace.numel()))
+    _tri_grid_build("mesh_ray", MESH_RAY_MAX_G, vertices, triangles, bmin, bmax, G, pairs, workspace)
 
 
 def mesh_ray_cast(origins, dirs, T, G, pairs, workspace, t_min, t_max, t, tri, bary):
@@ -1975,40 +1988,19 @@ MESH_WINDING_TOTALS = ("inside", "positive", "leaky_columns", "max_abs")  # the 
 def mesh_winding_workspace_bytes(T, G, pairs):
     """pvd_mesh_winding_workspace_bytes: bytes of workspace mesh_winding_build and the two queries need for T triangles, G^2 cells and
     `pairs` (cell, triangle) pairs (the first total of mesh_winding_count)."""
-    ok = 0 <= int(T) < 2 ** 32 and 0 <= int(G) < 2 ** 32 and 0 <= int(pairs) < 2 ** 64
-    n = int(_lib.pvd_mesh_winding_workspace_bytes(_u32(T), _u32(G), _u64(pairs))) if ok else 0
-    if n == 0:
-        raise PvdHipError("pvd_mesh_winding_workspace_bytes: G must be 1 .. %d, T and pairs below 2^31, got T=%d G=%d pairs=%d"
-                          % (MESH_WINDING_MAX_G, int(T), int(G), int(pairs)))
-    return n
-
-
-def _mesh_winding_mesh(vertices, triangles, bmin, bmax, G):
-    V, T = _mesh_and_box(vertices, triangles, bmin, bmax)
-    if not 1 <= int(G) <= MESH_WINDING_MAX_G:
-        raise PvdHipError("G must be 1 .. %d, got %d" % (MESH_WINDING_MAX_G, int(G)))
-    return V, T
+    return _tri_grid_workspace_bytes("mesh_winding", MESH_WINDING_MAX_G, T, G, pairs)
 
 
 def mesh_winding_count(vertices, triangles, bmin, bmax, G, totals):
     """pvd_mesh_winding_count: totals int64 [2] on the device <- (the (cell, triangle) pairs, the outside triangles) of the mesh
     (vertices [V,3] f32, triangles [T,3] int32) over G^2 cells of the x / y extent of the box bmin .. bmax (device f32 [3] each)."""
-    dev = _dev(vertices, triangles, bmin, bmax, totals)
-    V, T = _mesh_winding_mesh(vertices, triangles, bmin, bmax, G)
-    _want(totals, torch.int64, "totals")
-    if totals.numel() < 2:
-        raise PvdHipError("totals must hold 2 int64 values")
-    _call("pvd_mesh_winding_count", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _p(totals))
+    _tri_grid_count("mesh_winding", MESH_WINDING_MAX_G, vertices, triangles, bmin, bmax, G, totals)
 
 
 def mesh_winding_build(vertices, triangles, bmin, bmax, G, pairs, workspace):
     """pvd_mesh_winding_build: bins the valid triangles of the SAME mesh, box and G as mesh_winding_count, with the `pairs` it left, and
     leaves in the workspace (uint8, mesh_winding_workspace_bytes(T, G, pairs)) what mesh_winding_points / _lattice need."""
-    dev = _dev(vertices, triangles, bmin, bmax, workspace)
-    V, T = _mesh_winding_mesh(vertices, triangles, bmin, bmax, G)
-    _mesh_workspace(workspace, mesh_winding_workspace_bytes(T, G, pairs), "mesh_winding_workspace_bytes(T, G, pairs)")
-    _call("pvd_mesh_winding_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(bmin), _p(bmax), _u32(G), _u64(pairs),
-          _p(workspace), ctypes.c_size_t(workspace.numel()))
+    _tri_grid_build("mesh_winding", MESH_WINDING_MAX_G, vertices, triangles, bmin, bmax, G, pairs, workspace)
 
 
 def mesh_winding_points(points, T, G, pairs, workspace, winding):

@@ -65,7 +65,9 @@ def test_the_binding_lists_them_in_a_tuple_of_their_own(hip_lib_built):
 def test_the_source_is_in_the_makefile():
     mk = open(os.path.join(REPO, "aaai2023-pvd_amd", "csrc", "Makefile")).read()
     srcs = [ln for ln in mk.splitlines() if ln.startswith("SRCS")][0]
-    assert "mesh_ray.hip" in srcs.split() and "../../include/pvd_hip_mesh_ray.h" in mk
+    assert "mesh_ray.hip" in srcs.split() and "../../include/pvd_hip_mesh_ray.h" in mk and " mesh_tri_grid.h " in mk
+    # the grid is built by the header it shares with the winding numbers, not by a copy
+    assert "int classify(" not in open(os.path.join(REPO, "aaai2023-pvd_amd", "csrc", "mesh_ray.hip")).read()
 
 
 def test_the_workspace_size(hip_lib_built):

@@ -89,12 +89,13 @@ def test_the_source_and_the_header_are_in_the_makefile():
     mk = open(os.path.join(CSRC, "Makefile")).read()
     srcs = [ln for ln in mk.splitlines() if ln.startswith("SRCS")][0].split()
     assert "mesh_shtex.hip" in srcs and srcs.index("mesh_shtex.hip") == srcs.index("mesh_tex.hip") + 1
-    assert " pvd_hip_mesh_shtex.h " in mk
+    assert " pvd_hip_mesh_shtex.h " in mk and " mesh_atlas.h " in mk
     assert "-ffp-contract=off" in [ln for ln in mk.splitlines() if ln.startswith("FLAGS")][0]
     src = open(os.path.join(CSRC, "mesh_shtex.hip")).read()
     assert '#include "pvd_hip_mesh_shtex.h"' in src and "#pragma clang fp contract(off)" in src
     assert "fma(" not in src and "fmaf(" not in src and "__shared__" not in src and "atomic" not in src.replace("no atomics", "")
     assert "sh_basis.inc" not in src and "pvd_sh_basis" not in src  # the fused basis of the direction encoder is not this one
+    assert "void texel_of(" not in src  # the atlas addressing is csrc/mesh_atlas.h's, shared with mesh_tex.hip, not a copy
     for L in "1234":  # the band count is a template parameter with four instantiations
         assert "k_st_sample<%s>" % L in src
 

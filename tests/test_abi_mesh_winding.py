@@ -79,10 +79,13 @@ def test_the_source_and_the_header_are_in_the_makefile():
     mk = open(os.path.join(REPO, "aaai2023-pvd_amd", "csrc", "Makefile")).read()
     srcs = [ln for ln in mk.splitlines() if ln.startswith("SRCS")][0]
     assert "mesh_winding.hip" in srcs.split() and "../../include/pvd_hip_mesh_winding.h" in mk
+    assert " mesh_tri_grid.h " in mk
     src = open(os.path.join(REPO, "aaai2023-pvd_amd", "csrc", "mesh_winding.hip")).read()
-    # the shared scan, not a further copy; the products are never fused by the source
-    assert '#include "block_scan.h"' in src and "k_scan<" in src and "wave_scan(" in src and "__shfl_up" not in src
-    assert "fma(" not in src and "fmaf(" not in src
+    grid = open(os.path.join(REPO, "aaai2023-pvd_amd", "csrc", "mesh_tri_grid.h")).read()
+    # the shared scan, not a further copy (launched by the shared build of the grid); the products are never fused by the source
+    assert '#include "block_scan.h"' in grid and "k_scan<" in grid and "wave_scan(" in src and "__shfl_up" not in src
+    assert "int classify(" not in src
+    assert "fma(" not in src and "fmaf(" not in src and "fma(" not in grid and "fmaf(" not in grid
 
 
 def test_the_workspace_size(hip_lib_built):
