@@ -22,6 +22,7 @@ def _samples(N=2048, seed=0):
 
 @pytest.mark.parametrize("bg_kind", ["tensor", "scalar"])
 def test_composite_bg_matches_composition(bg_kind):
+    """fused against unfused launches of the same kernel; the accuracy statement is tests/test_hip_composite_fp64.py (float64, per element)"""
     import raymarching
     dev = torch.device("cuda:0")
     xyzs, deltas, rays, nears, fars = _samples()

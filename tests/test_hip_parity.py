@@ -157,6 +157,7 @@ def _samples(N, seed, dev):
 
 
 def test_composite_train_fwd_bwd(hip, dev):
+    """parity with the float32 sequential oracle (max-norm); the accuracy statement is tests/test_hip_composite_fp64.py (float64, per element)"""
     N = 4096
     xyzs, dirs, deltas, rays = _samples(N, 7, dev)
     M = xyzs.shape[0]
