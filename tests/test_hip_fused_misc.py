@@ -151,7 +151,8 @@ def test_objective_finished_inside_the_backward_launch_is_bit_identical():
 
 def test_flat_adamw_matches_torch_fused_adamw():
     """Same parameters / gradients through torch.optim.AdamW(fused) and FlatAdamW, with GradScaler-style
-    grad_scale, a skipped (found_inf) step and two learning-rate groups, over several steps."""
+    grad_scale, a skipped (found_inf) step and two learning-rate groups, over several steps.
+    The accuracy statement, per element and per call, is tests/test_hip_adamw_fp64.py (float64 reference, derived bound)."""
     from pvd.flat_adamw import FlatAdamW
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -194,7 +195,8 @@ def test_flat_adamw_matches_torch_fused_adamw():
 
 def test_flat_adamw_device_schedule_l1_and_finite_check():
     """FlatAdamW with the cosine / exponential schedule evaluated inside the update kernel and the L1
-    regulariser folded into it == torch AdamW + torch LR scheduler + autograd of weight * sum mean|t|."""
+    regulariser folded into it == torch AdamW + torch LR scheduler + autograd of weight * sum mean|t|.
+    The accuracy statement, per element and per call, is tests/test_hip_adamw_fp64.py (float64 reference, derived bound)."""
     import math
     import pvd_hip
     from pvd.flat_adamw import DeviceSchedule, FlatAdamW, FlatGradScaler
@@ -661,7 +663,8 @@ def test_composite_bg_backward_fresh_gradients(budget):
 def test_adamw_cold_groups_are_bit_identical_to_the_dense_update():
     """pvd_adamw_extras.cold_bits: groups of 4 parameters whose gradient and moments are zero for good get the weight decay
     alone, without g / m / v being read or written -- the very bits the dense kernel produces (g = m = v = 0 makes the Adam
-    term exactly zero).  Six steps with a schedule, a GradScaler scale, L1 on a warm range and an inf step in between."""
+    term exactly zero).  Six steps with a schedule, a GradScaler scale, L1 on a warm range and an inf step in between.
+    The forms are compared with each other here; each against float64 in tests/test_hip_adamw_fp64.py."""
     import pvd_hip
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
