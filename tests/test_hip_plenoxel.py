@@ -2,7 +2,9 @@
 reference's own formulation -- a 3-D F.grid_sample(align_corners=True) over the [1,C,D,H,W] parameter, clamp,
 trunc_exp, SH dot product, sigmoid (distill_mutual/network.py:311-322, 383-409) -- evaluated by PyTorch in
 float32 on the same device (and float64 on the CPU as an absolute anchor).
-Tolerance: fp32 with a different summation order; north_star's bar is 1e-4 on sigma / RGB."""
+Tolerance: fp32 with a different summation order; north_star's bar is 1e-4 on sigma / RGB.
+These are max-norm checks on random points; the accuracy statement -- element by element against float64 under a derived bound,
+every move of the register window scripted -- is tests/test_hip_plenoxel_fp64.py."""
 import numpy as np
 import pytest
 import torch
@@ -59,6 +61,7 @@ def _ref_head(vol, x, d, degree, cmin, cmax):
 @pytest.mark.parametrize("degree,dims,coherent", [(3, (128, 128, 128), True), (3, (128, 128, 128), False), (2, (20, 24, 28), False),
                                                    (1, (9, 7, 5), False), (3, (33, 17, 65), True)])
 def test_plenoxel_features_match_grid_sample(degree, dims, coherent):
+    """max norm against float32 grid_sample through the autograd wrapper; accuracy statement: tests/test_hip_plenoxel_fp64.py"""
     import plenoxel
     vol = _volume(degree, dims).requires_grad_(True)
     M = 64 * 700 + 13 if not coherent else 64 * 700
@@ -90,6 +93,7 @@ def test_plenoxel_features_match_grid_sample(degree, dims, coherent):
 
 @pytest.mark.parametrize("degree,coherent", [(3, True), (3, False), (2, False), (1, True)])
 def test_plenoxel_head_forward_backward(degree, coherent):
+    """max norm against the torch formulation through the autograd wrapper; accuracy statement: tests/test_hip_plenoxel_fp64.py"""
     import plenoxel
     dims = (64, 48, 56)
     vol = _volume(degree, dims, seed=3, scale=2.0).requires_grad_(True)  # scale 2: the clamp at [-2, 7] is active
