@@ -210,12 +210,19 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
             col = vertex_colors(model, vertices, nrm)
     else:
         vertices, triangles = extract_mesh(u, threshold, lo, hi)
+    return _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, dict(field=u, threshold=float(threshold), counts=counts),
+                           smooth, smooth_lambda, smooth_mu, simplify, clean, min_shell_triangles, largest_shell_only, texture, texture_sh)
+
+
+def _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, extra, smooth, smooth_lambda, smooth_mu, simplify, clean,
+                    min_shell_triangles, largest_shell_only, texture, texture_sh):
+    """The tail extract_surface and extract_surface_tsdf share: smoothing, the dict (with `extra` after the four mesh entries), the
+    simplification, the clean-up and the texture bake, in extract_surface's order and with its meaning."""
     if int(smooth) > 0:
         vertices = smooth_mesh(vertices, triangles, iterations=int(smooth), lam=smooth_lambda, mu=smooth_mu, bmin=lo, bmax=hi)
         if normals:
             nrm = face_vertex_normals(vertices, triangles)
-    out = dict(vertices=vertices, triangles=triangles, normals=nrm if normals else None, colors=col, field=u,
-               threshold=float(threshold), counts=counts)
+    out = dict(vertices=vertices, triangles=triangles, normals=nrm if normals else None, colors=col, **extra)
     if int(smooth) > 0:
         out["smoothed"] = int(smooth)
     if int(simplify) > 0:
@@ -1340,3 +1347,187 @@ def sample_sh_texture(texture, S, T, tri, bary, dirs, bg_color=1.0):
     color = torch.empty(int(tri.shape[0]), 3, dtype=torch.float32, device=dev)
     pvd_hip.mesh_shtex_sample(texture, int(T), int(S), L, tri, bary, dirs, bg, color)
     return color.reshape(shape + (3,))
+
+
+# ------------------------------------------------------------------------------------------- depth-map fusion (csrc/pvd_hip_mesh_tsdf.h)
+class TSDFVolume:
+    """The accumulators of a truncated signed distance volume over the R^3 lattice of the box bmin .. bmax (density_field's lattice):
+    acc_d [R,R,R] (sum of w t), acc_w [R,R,R] (sum of w) and acc_c [R,R,R,3] (sum of w rgb; None without colour), f32 on the device,
+    with the truncation distance tau and the number of views integrated so far.  Made by tsdf_volume."""
+
+    def __init__(self, R, bmin, bmax, tau, acc_d, acc_w, acc_c):
+        self.R, self.bmin, self.bmax, self.tau = R, bmin, bmax, tau
+        self.acc_d, self.acc_w, self.acc_c = acc_d, acc_w, acc_c
+        self.views = 0
+
+
+def tsdf_volume(R, bmin, bmax, tau=None, with_color=True, device=None):
+    """An empty TSDFVolume.  tau defaults to 3 lattice spacings of the longest box axis."""
+    R = int(R)
+    if R < 2:
+        raise ValueError("R must be at least 2")
+    if device is None:
+        device = bmin.device if torch.is_tensor(bmin) else torch.device("cuda", torch.cuda.current_device())
+    lo, hi = _box(bmin, bmax, device)
+    if tau is None:
+        tau = 3.0 * float((hi - lo).abs().max()) / (R - 1)
+    tau = float(tau)
+    if not 0.0 < tau < float("inf"):
+        raise ValueError("tau must be positive and finite")
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=device)  # noqa: E731
+    return TSDFVolume(R, lo, hi, tau, z(R, R, R), z(R, R, R), z(R, R, R, 3) if with_color else None)
+
+
+def tsdf_integrate(acc, depth, poses, intrinsics, color=None, weight=None):
+    """Adds the views to the volume `acc` (csrc/pvd_hip_mesh_tsdf.h, "Integrate"; one launch): depth [V,H,W] -- the distance along the
+    unit ray of every pixel, +inf where the ray left the scene (free space), NaN or <= 0 where nothing is known --, poses [V,4,4]
+    cam2world as get_rays takes them, intrinsics (fx, fy, cx, cy) for all views or [V,4], color [V,H,W,3] and weight [V,H,W] optional.
+    A volume with colour takes views WITH colour only (ValueError otherwise: a view that added its weight but no colour would darken
+    tsdf_vertex_colors, which divides the colour sums by the weight sums); a volume without colour ignores `color`.  Views may arrive in any number of calls: the result is, bit for
+    bit, that of one call with all of them in the same order."""
+    import pvd_hip
+    dev = acc.acc_d.device
+    f = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).contiguous()  # noqa: E731
+    depth, poses, color, weight = f(depth), f(poses), f(color), f(weight)
+    V = int(depth.shape[0])
+    intrinsics = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev)
+    if intrinsics.dim() == 1:
+        intrinsics = intrinsics[None, :].expand(V, 4)
+    if acc.acc_c is not None and color is None:
+        raise ValueError("the volume accumulates colour: every call needs `color` (or make it with tsdf_volume(with_color=False))")
+    with_color = acc.acc_c is not None
+    pvd_hip.mesh_tsdf_integrate(depth, color if with_color else None, weight, poses, intrinsics.contiguous(), acc.R, acc.bmin, acc.bmax,
+                                acc.tau, acc.acc_d, acc.acc_w, acc.acc_c if with_color else None)
+    acc.views += V
+    return acc
+
+
+def tsdf_field(acc, min_weight=1.0, unknown=-1.0, return_totals=False):
+    """field [R,R,R] f32 on the device, in [-1, 1] and POSITIVE OUTSIDE: acc_d / acc_w where acc_w >= min_weight, `unknown` elsewhere.
+    unknown = -1 treats what no view observed as solid -- the interior behind the truncation band never is, so a watertight mesh needs
+    it, and it also fills what no camera covers; unknown = +1 treats it as empty and leaves an inner shell where the band ends.
+    extract_mesh meshes field > thresh as inside: hand it -field and the level 0 (extract_surface_tsdf does).  return_totals=True:
+    (field, dict(observed, observed_inside, unknown)), one read-back."""
+    import pvd_hip
+    field = torch.empty(acc.R, acc.R, acc.R, dtype=torch.float32, device=acc.acc_d.device)
+    totals = torch.empty(3, dtype=torch.int64, device=field.device)
+    pvd_hip.mesh_tsdf_finalize(acc.acc_d, acc.acc_w, acc.R, float(min_weight), float(unknown), field, totals)
+    if not return_totals:
+        return field
+    return field, dict(zip(pvd_hip.MESH_TSDF_TOTALS, (int(v) for v in totals.tolist())))
+
+
+def tsdf_vertex_colors(acc, vertices, min_weight=1.0):
+    """[V,3] f32 in [0,1] on the device: the fused colour at every vertex -- the trilinear blend of acc_c / acc_w over the observed ones
+    of the 8 lattice points around it, renormalised; 0 for a vertex that is not finite, outside the box, or with no observed corner."""
+    import pvd_hip
+    if acc.acc_c is None:
+        raise ValueError("the volume was made without colour")
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    colors = torch.empty_like(vertices)
+    pvd_hip.mesh_tsdf_sample_color(acc.acc_c, acc.acc_w, acc.R, acc.bmin, acc.bmax, float(min_weight), vertices, colors)
+    return colors
+
+
+def tsdf_poses(n=64, radius=4.0, scale=0.8):
+    """[n,4,4] f32 (a host tensor): the default cameras of extract_surface_tsdf -- pose_spherical views through nerf_matrix_to_ngp, as
+    the synthetic scenes have them, looking at the origin from the points of exposure_directions' Fibonacci sphere: the elevation
+    phi_i = -asin(z_i) covers both hemispheres, the azimuth theta_i is the sphere's."""
+    import numpy as np
+
+    from .scene import nerf_matrix_to_ngp, pose_spherical
+    d = exposure_directions(int(n)).double().numpy()
+    theta = np.degrees(np.arctan2(d[:, 1], d[:, 0]))
+    phi = -np.degrees(np.arcsin(np.clip(d[:, 2], -1.0, 1.0)))
+    return torch.from_numpy(np.stack([nerf_matrix_to_ngp(pose_spherical(float(t), float(p), float(radius)), scale)
+                                      for t, p in zip(theta, phi)]).astype(np.float32))
+
+
+@torch.no_grad()
+def render_depth_maps(model, poses, intrinsics, H, W, min_opacity=0.5, free_opacity=0.05, max_steps=1024, ray_batch=1 << 16):
+    """dict(depth [V,H,W], color [V,H,W,3], opacity [V,H,W]), f32 on the device: what tsdf_integrate wants, rendered by `model` on its
+    own occupancy grid.  Per ray, with weights_sum and the raw depth sum of composite_rays_train over march_rays_train's samples
+    (all rays, no jitter; the model's forward under fp16 autocast, as evaluate_views renders): depth = near + raw / weights_sum -- the
+    expected distance along the unit ray, given that the ray ended; the training marcher counts a sample's t from the ray's start,
+    which without jitter is its near, so the raw sum is sum w (t - near) -- where weights_sum >= min_opacity; +inf (the ray left the
+    scene) where weights_sum < free_opacity; NaN (no observation) in between.  The colour is un-premultiplied the same way and 0 elsewhere.
+    (The inference branch of render returns a depth clamped and normalised to the slab and not divided by the opacity, and no opacity:
+    not this.)  `ray_batch` rays are marched at a time, so an 800 x 800 view needs no more memory than a small one."""
+    from .scene import get_rays
+    rm = model.rm
+    dev = model.aabb_infer.device
+    poses = torch.as_tensor(poses, dtype=torch.float32, device=dev)
+    V, H, W = int(poses.shape[0]), int(H), int(W)
+    intr = torch.as_tensor(intrinsics, dtype=torch.float32).reshape(-1, 4)
+    depth = torch.empty(V, H * W, dtype=torch.float32, device=dev)
+    opacity = torch.empty(V, H * W, dtype=torch.float32, device=dev)
+    color = torch.empty(V, H * W, 3, dtype=torch.float32, device=dev)
+    scale = float(model.density_scale)
+    for v in range(V):
+        rays = get_rays(poses[v:v + 1], tuple(float(x) for x in intr[min(v, intr.shape[0] - 1)]), H, W)
+        o, d = rays["rays_o"].reshape(-1, 3).contiguous(), rays["rays_d"].reshape(-1, 3).contiguous()
+        for s in range(0, H * W, int(ray_batch)):
+            ob, db = o[s:s + int(ray_batch)].contiguous(), d[s:s + int(ray_batch)].contiguous()
+            nears, fars = rm.near_far_from_aabb(ob, db, model.aabb_infer, model.min_near)
+            xyzs, dirs, deltas, table = rm.march_rays_train(ob, db, model.bound, model.density_bitfield, model.cascade, model.grid_size,
+                                                            nears, fars, None, -1, False, 128, True, 0, int(max_steps))
+            with torch.autocast("cuda", dtype=torch.float16):
+                sigmas, rgbs = model(xyzs, dirs)
+            if scale != 1:
+                sigmas = scale * sigmas
+            ws, wt, img = rm.composite_rays_train(sigmas.float(), rgbs.float(), deltas, table)
+            solid, free = ws >= float(min_opacity), ws < float(free_opacity)
+            nan = torch.full_like(ws, float("nan"))
+            depth[v, s:s + ob.shape[0]] = torch.where(solid, nears + wt / ws, torch.where(free, torch.full_like(ws, float("inf")), nan))
+            color[v, s:s + ob.shape[0]] = torch.where(solid[:, None], (img / ws[:, None]).clamp(0.0, 1.0), torch.zeros_like(img))
+            opacity[v, s:s + ob.shape[0]] = ws
+    return dict(depth=depth.view(V, H, W), color=color.view(V, H, W, 3), opacity=opacity.view(V, H, W))
+
+
+def extract_surface_tsdf(model, poses=None, intrinsics=None, H=400, W=400, resolution=256, tau=None, bmin=None, bmax=None,
+                         views_per_batch=8, min_weight=1.0, unknown=-1.0, min_opacity=0.5, free_opacity=0.05, min_points=0,
+                         largest_only=False, normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53,
+                         clean=False, min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0):
+    """extract_surface with the geometry taken from what the model RENDERS: depth and colour maps of `poses` (render_depth_maps;
+    default tsdf_poses(), with intrinsics of a 50 degree field of view where none are given) are fused into a TSDFVolume over the box
+    (default model.aabb_infer), views_per_batch at a time, and the zero level of tsdf_field is meshed -- where the model's rays end,
+    whatever its density scale or threshold, with what any camera sees through carved empty.  The dict has extract_surface's shape:
+    vertices, triangles, normals (the gradient of the fused field: extract_mesh's with_normals), colors (tsdf_vertex_colors: the
+    fused colours, no second pass over the model), field (the TSDF, positive outside), threshold = 0.0 and counts, plus tsdf_totals
+    (tsdf_field's) and views.  min_points, largest_only, smooth, simplify, clean, texture and texture_sh mean exactly what they mean in
+    extract_surface and go through the same functions."""
+    import math
+    aabb = model.aabb_infer
+    lo = aabb[:3] if bmin is None else bmin
+    hi = aabb[3:] if bmax is None else bmax
+    if poses is None:
+        poses = tsdf_poses()
+    if intrinsics is None:
+        focal = 0.5 * W / math.tan(math.radians(25.0))
+        intrinsics = (focal, focal, 0.5 * W, 0.5 * H)
+    poses = torch.as_tensor(poses, dtype=torch.float32, device=aabb.device)
+    intr = torch.as_tensor(intrinsics, dtype=torch.float32).reshape(-1, 4)
+    acc = tsdf_volume(resolution, lo, hi, tau=tau, with_color=bool(colors), device=aabb.device)
+    step = max(int(views_per_batch), 1)
+    for s in range(0, int(poses.shape[0]), step):
+        maps = render_depth_maps(model, poses[s:s + step], intr[s:s + step] if intr.shape[0] > 1 else intr, H, W, min_opacity=min_opacity,
+                                 free_opacity=free_opacity)
+        tsdf_integrate(acc, maps["depth"], poses[s:s + step], intr[s:s + step] if intr.shape[0] > 1 else intr[0],
+                       color=maps["color"] if colors else None)
+    field, totals = tsdf_field(acc, min_weight=min_weight, unknown=unknown, return_totals=True)
+    u = -field  # extract_mesh: inside is u > 0
+    counts = None
+    if int(min_points) > 0 or largest_only:
+        stats, kept = _drop(u, int(resolution), 0.0, min_points, largest_only, u)
+        counts = (int(stats[0]),) + tuple(int(v) for v in kept.tolist())
+        field = -u
+    nrm = col = None
+    if normals or colors:
+        vertices, triangles, nrm = extract_mesh(u, 0.0, lo, hi, with_normals=True)
+        if colors:
+            col = tsdf_vertex_colors(acc, vertices, min_weight=min_weight)
+    else:
+        vertices, triangles = extract_mesh(u, 0.0, lo, hi)
+    extra = dict(field=field, threshold=0.0, counts=counts, tsdf_totals=totals, views=acc.views)
+    return _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, extra, smooth, smooth_lambda, smooth_mu, simplify, clean,
+                           min_shell_triangles, largest_shell_only, texture, texture_sh)

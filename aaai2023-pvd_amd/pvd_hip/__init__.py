@@ -122,13 +122,15 @@ ENTRY_POINTS_MESH_TEX = ("pvd_mesh_tex_layout", "pvd_mesh_tex_points", "pvd_mesh
 ENTRY_POINTS_MESH_EXPOSE = ("pvd_mesh_expose",)
 # ... and the view-dependent atlas of csrc/pvd_hip_mesh_shtex.h (tests/test_abi_mesh_shtex.py)
 ENTRY_POINTS_MESH_SHTEX = ("pvd_mesh_shtex_basis", "pvd_mesh_shtex_dirs", "pvd_mesh_shtex_project", "pvd_mesh_shtex_sample")
+# ... and the depth-map fusion of csrc/pvd_hip_mesh_tsdf.h (tests/test_abi_mesh_tsdf.py)
+ENTRY_POINTS_MESH_TSDF = ("pvd_mesh_tsdf_integrate", "pvd_mesh_tsdf_finalize", "pvd_mesh_tsdf_sample_color")
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
               + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING + ENTRY_POINTS_MESH_TEX
-              + ENTRY_POINTS_MESH_EXPOSE + ENTRY_POINTS_MESH_SHTEX):
+              + ENTRY_POINTS_MESH_EXPOSE + ENTRY_POINTS_MESH_SHTEX + ENTRY_POINTS_MESH_TSDF):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -2155,6 +2157,91 @@ def mesh_shtex_sample(texture, T, S, L, tri, bary, dirs, bg3, color):
     if bary.numel() != 2 * N or dirs.numel() != 3 * N or color.numel() != 3 * N or bg3.numel() < 3:
         raise PvdHipError("bary must hold 2 N, dirs and color 3 N and bg3 3 values")
     _call("pvd_mesh_shtex_sample", dev, _p(texture), _u32(T), _u32(S), _u32(L), _p(tri), _p(bary), _p(dirs), _u32(N), _p(bg3), _p(color))
+
+
+# --------------------------------------------------------------------------- depth-map fusion (csrc/pvd_hip_mesh_tsdf.h)
+MESH_TSDF_MAX_R = 1024  # PVD_MESH_TSDF_MAX_R: points per lattice axis, 2 .. 1024
+MESH_TSDF_MAX_SIDE = 16384  # PVD_MESH_TSDF_MAX_SIDE: the largest height or width of a depth image
+MESH_TSDF_TOTALS = ("observed", "observed_inside", "unknown")  # the three totals of mesh_tsdf_finalize
+
+
+def _tsdf_lattice(R):
+    if not 2 <= int(R) <= MESH_TSDF_MAX_R:
+        raise PvdHipError("R must be 2 .. %d, got %d" % (MESH_TSDF_MAX_R, int(R)))
+    return int(R)
+
+
+def _tsdf_positive(x, name):
+    x = float(x)
+    if not (0.0 < x < float("inf")):
+        raise PvdHipError("%s must be positive and finite, got %r" % (name, x))
+    return x
+
+
+def mesh_tsdf_integrate(depth, color, weight, poses, intrinsics, R, bmin, bmax, tau, acc_d, acc_w, acc_c):
+    """pvd_mesh_tsdf_integrate: acc_d [R,R,R] f32 (sum of w t), acc_w [R,R,R] f32 (sum of w) and acc_c [R,R,R,3] f32 or None (sum of
+    w rgb) += the views depth [V,H,W] f32 (distance along the unit ray; +inf: free space; NaN or <= 0: nothing), color [V,H,W,3] f32 or
+    None, weight [V,H,W] f32 or None, poses [V,4,4] f32 (cam2world, get_rays' convention), intrinsics [V,4] f32 (fx, fy, cx, cy), over the
+    lattice of the box bmin .. bmax (device f32 [3] each) with the truncation distance tau.  Colour needs both color and acc_c."""
+    dev = _dev(depth, color, weight, poses, intrinsics, bmin, bmax, acc_d, acc_w, acc_c)
+    _f32_all(depth=depth, poses=poses, intrinsics=intrinsics, bmin=bmin, bmax=bmax, acc_d=acc_d, acc_w=acc_w)
+    R = _tsdf_lattice(R)
+    tau = _tsdf_positive(tau, "tau")
+    if depth.dim() != 3:
+        raise PvdHipError("depth must be [V,H,W]")
+    V, H, W = (int(v) for v in depth.shape)
+    if not (1 <= H <= MESH_TSDF_MAX_SIDE and 1 <= W <= MESH_TSDF_MAX_SIDE):
+        raise PvdHipError("H and W must be 1 .. %d, got %d x %d" % (MESH_TSDF_MAX_SIDE, H, W))
+    if tuple(poses.shape) != (V, 4, 4) or tuple(intrinsics.shape) != (V, 4):
+        raise PvdHipError("poses must be [V,4,4] and intrinsics [V,4] for V = %d" % V)
+    if (color is None) != (acc_c is None):
+        raise PvdHipError("color and acc_c go together")
+    if color is not None:
+        _f32_all(color=color, acc_c=acc_c)
+        if tuple(color.shape) != (V, H, W, 3) or acc_c.numel() != 3 * R ** 3:
+            raise PvdHipError("color must be [V,H,W,3] and acc_c hold 3 R^3 values")
+    if weight is not None:
+        _f32_all(weight=weight)
+        if tuple(weight.shape) != (V, H, W):
+            raise PvdHipError("weight must be [V,H,W]")
+    if bmin.numel() < 3 or bmax.numel() < 3 or acc_d.numel() != R ** 3 or acc_w.numel() != R ** 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats, acc_d and acc_w R^3 values")
+    _call("pvd_mesh_tsdf_integrate", dev, _p(depth), _p(color), _p(weight), _p(poses), _p(intrinsics), _u32(V), _u32(H), _u32(W), _u32(R),
+          _p(bmin), _p(bmax), ctypes.c_float(tau), _p(acc_d), _p(acc_w), _p(acc_c))
+
+
+def mesh_tsdf_finalize(acc_d, acc_w, R, min_weight, unknown, field, totals):
+    """pvd_mesh_tsdf_finalize: field [R,R,R] f32 <- clamp(acc_d / acc_w, -1, 1) where acc_w >= min_weight, `unknown` elsewhere (positive
+    outside); totals int64 [3] on the device <- MESH_TSDF_TOTALS."""
+    dev = _dev(acc_d, acc_w, field, totals)
+    _f32_all(acc_d=acc_d, acc_w=acc_w, field=field)
+    _want(totals, torch.int64, "totals")
+    R = _tsdf_lattice(R)
+    min_weight = _tsdf_positive(min_weight, "min_weight")
+    unknown = float(unknown)
+    if not abs(unknown) < float("inf"):
+        raise PvdHipError("unknown must be finite, got %r" % unknown)
+    if acc_d.numel() != R ** 3 or acc_w.numel() != R ** 3 or field.numel() != R ** 3 or totals.numel() < 3:
+        raise PvdHipError("acc_d, acc_w and field must hold R^3 values and totals 3")
+    _call("pvd_mesh_tsdf_finalize", dev, _p(acc_d), _p(acc_w), _u32(R), ctypes.c_float(min_weight), ctypes.c_float(unknown), _p(field),
+          _p(totals))
+
+
+def mesh_tsdf_sample_color(acc_c, acc_w, R, bmin, bmax, min_weight, points, colors):
+    """pvd_mesh_tsdf_sample_color: colors [N,3] f32 <- the trilinear blend of acc_c / acc_w over the observed (acc_w >= min_weight) ones
+    of the 8 lattice points around every row of points [N,3] f32, renormalised and clamped to [0, 1]; 0 for a row that is not finite,
+    outside the box bmin .. bmax, or with no observed corner."""
+    dev = _dev(acc_c, acc_w, bmin, bmax, points, colors)
+    _f32_all(acc_c=acc_c, acc_w=acc_w, bmin=bmin, bmax=bmax, points=points, colors=colors)
+    R = _tsdf_lattice(R)
+    min_weight = _tsdf_positive(min_weight, "min_weight")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise PvdHipError("points must be [N,3]")
+    N = int(points.shape[0])
+    if colors.numel() != 3 * N or acc_c.numel() != 3 * R ** 3 or acc_w.numel() != R ** 3 or bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("colors must hold 3 N values, acc_c 3 R^3, acc_w R^3, bmin / bmax 3")
+    _call("pvd_mesh_tsdf_sample_color", dev, _p(acc_c), _p(acc_w), _u32(R), _p(bmin), _p(bmax), ctypes.c_float(min_weight), _p(points), _u32(N),
+          _p(colors))
 
 
 # --------------------------------------------------------------------------- Taubin smoothing (include/pvd_hip_mesh_smooth.h)

@@ -8,6 +8,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
                               [--smooth N [--smooth-lambda L --smooth-mu M] [--smooth-report]] [--render-check N]
                               [--clean [--min-shell N] [--largest-shell-only]] [--topology-report] [--texture S [--texture-sh L]]
                               [--cull-hidden {shells,triangles} [--exposure-dirs D --exposure-samples S] [--exposure-report]]
+                              [--tsdf N [--tsdf-res HxW] [--tsdf-trunc K]]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
 The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
@@ -52,7 +53,15 @@ and dropped, the ray totals; with --texture also atlas_before and atlas_after, [
 spherical-harmonics coefficients per channel and texel, fitted to the model's colour along 64 directions.  The .png / .obj / .mtl are
 written from its view-independent part; the coefficients go to <stem>.shtex.npy ([height, width, L * L, 3] float32, numpy.save) with a
 one-line JSON sidecar <stem>.shtex.json carrying S, L and T.  With --render-check N a fourth render is reported next to the three: the
-SH-textured mesh, coloured at every pixel for that pixel's ray (the flat atlas of the first line is then baked as well, for the check only)."""
+SH-textured mesh, coloured at every pixel for that pixel's ray (the flat atlas of the first line is then baked as well, for the check only).
+--tsdf N takes the geometry from what the model RENDERS instead of from a density level: depth and colour maps of N cameras on a Fibonacci
+sphere (pvd/mesh.py: tsdf_poses, render_depth_maps; --tsdf-res HxW pixels each, default 400x400) are fused into a truncated signed
+distance volume on the same lattice (tsdf_integrate, csrc/mesh_tsdf.hip; the truncation distance is --tsdf-trunc K lattice spacings,
+default 3) and its zero level is meshed (extract_surface_tsdf).  No density threshold takes part, what any camera sees through is
+carved empty, and --colors are the fused colours of the views -- except with --cull-hidden, which takes the colours after the cull, from
+the model's colour head at the vertices that are left, as it does without --tsdf (textures are always baked from the model).  Every other
+flag works as before, on that mesh; --threshold is ignored.
+With --render-check the line's mean |depth difference| then measures the fused surface against the model's own composited depth."""
 import argparse
 import json
 import os
@@ -66,8 +75,8 @@ sys.path[:0] = [REPO, os.path.join(REPO, "aaai2023-pvd_amd")]
 
 from pvd.checkpoint import load_student_checkpoint  # noqa: E402
 from pvd.config import PVDConfig  # noqa: E402
-from pvd.mesh import (bake_texture, compare_meshes, default_threshold, extract_mesh, extract_surface, mesh_topology, render_mesh, smooth_mesh,  # noqa: E402
-                      write_obj, write_ply, write_png)
+from pvd.mesh import (bake_texture, compare_meshes, default_threshold, extract_mesh, extract_surface, extract_surface_tsdf, mesh_topology,  # noqa: E402
+                      render_mesh, smooth_mesh, tsdf_poses, write_obj, write_ply, write_png)
 from pvd.ops import hip_ops  # noqa: E402
 from pvd.workload import make_model  # noqa: E402
 
@@ -188,7 +197,16 @@ def main():
     ap.add_argument("--exposure-dirs", type=int, default=64, metavar="D", help="with --cull-hidden: directions of the Fibonacci sphere (1 .. 1024)")
     ap.add_argument("--exposure-samples", type=int, default=1, choices=[1, 4], metavar="S", help="with --cull-hidden: points per triangle (1 or 4)")
     ap.add_argument("--exposure-report", action="store_true", help="with --cull-hidden: print cull_hidden's report as one JSON line")
+    ap.add_argument("--tsdf", type=int, default=0, metavar="N", help="fuse the model's depth maps from N views into a TSDF volume and mesh its zero level")
+    ap.add_argument("--tsdf-res", default="400x400", metavar="HxW", help="with --tsdf: the size of the rendered depth maps")
+    ap.add_argument("--tsdf-trunc", type=float, default=3.0, metavar="K", help="with --tsdf: the truncation distance in lattice spacings")
     a = ap.parse_args()
+    if a.tsdf < 0:
+        ap.error("--tsdf N: the number of views must not be negative")
+    if a.tsdf == 0 and (a.tsdf_res != "400x400" or a.tsdf_trunc != 3.0):
+        ap.error("--tsdf-res and --tsdf-trunc need --tsdf N")
+    if a.tsdf > 0 and not (a.tsdf_trunc > 0 and len(a.tsdf_res.lower().split("x")) == 2):
+        ap.error("--tsdf-res must be HxW and --tsdf-trunc positive")
     if a.cull_hidden is None and (a.exposure_report or a.exposure_dirs != 64 or a.exposure_samples != 1):
         ap.error("--exposure-dirs, --exposure-samples and --exposure-report need --cull-hidden")
     if not 1 <= a.exposure_dirs <= 1024:
@@ -212,19 +230,34 @@ def main():
               smooth_lambda=a.smooth_lambda, smooth_mu=a.smooth_mu, clean=a.clean, min_shell_triangles=a.min_shell,
               largest_shell_only=a.largest_shell_only)
     compare = a.texture > 0 and a.render_check > 0  # the three renders need the vertex colours too, written or not
+    surface = extract_surface
+    if a.tsdf > 0:  # the same dict from fused depth maps: the level is 0 of -field, the TSDF being positive outside
+        import math
+        th, tw = (int(v) for v in a.tsdf_res.lower().split("x"))
+        aabb = model.aabb_infer
+        focal = 0.5 * tw / math.tan(math.radians(25.0))
+        tau = a.tsdf_trunc * float((aabb[3:] - aabb[:3]).max()) / (a.resolution - 1)
+
+        def surface(model, threshold=None, **kwargs):
+            m = extract_surface_tsdf(model, tsdf_poses(a.tsdf), (focal, focal, 0.5 * tw, 0.5 * th), th, tw, tau=tau, **kwargs)
+            m["field"] = -m["field"]
+            return m
+        thresh = 0.0
     if a.cull_hidden:  # the geometry first; normals for the colours' sake too; colours and texture after the cull
-        m = extract_surface(model, normals=a.normals or a.colors or compare, colors=False, simplify=a.simplify, **kw)
+        m = surface(model, normals=a.normals or a.colors or compare, colors=False, simplify=a.simplify, **kw)
         exposure = cull_surface(model, m, a.cull_hidden, a.exposure_dirs, a.exposure_samples, colors=a.colors or compare, texture=a.texture,
                                 from_faces=a.smooth > 0, texture_sh=a.texture_sh)
     else:
-        m = extract_surface(model, normals=a.normals, colors=a.colors or compare, simplify=a.simplify,
-                            **(dict(texture=a.texture) if a.texture > 0 else {}), **(dict(texture_sh=a.texture_sh) if a.texture_sh > 0 else {}),
-                            **kw)
+        m = surface(model, normals=a.normals, colors=a.colors or compare, simplify=a.simplify,
+                    **(dict(texture=a.texture) if a.texture > 0 else {}), **(dict(texture_sh=a.texture_sh) if a.texture_sh > 0 else {}),
+                    **kw)
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
     write_ply(out, m["vertices"], m["triangles"], normals=m["normals"] if a.normals else None, colors=m["colors"] if a.colors else None)
     carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
     print("%s: %d vertices (%s), %d triangles at density %.6g, resolution %d"
           % (out, m["vertices"].shape[0], carries, m["triangles"].shape[0], thresh, a.resolution))
+    if a.tsdf > 0:
+        print("tsdf: %d views at %s, truncation %g spacings; voxels %s" % (m["views"], a.tsdf_res, a.tsdf_trunc, json.dumps(m["tsdf_totals"])))
     if filtering:
         print("components: %d found, %d kept, %d points kept" % m["counts"])
     if a.smooth > 0:
@@ -274,7 +307,7 @@ def main():
             print("%s.shtex.npy, .shtex.json: %d SH coefficients per channel and texel (L = %d); the .png holds the view-independent part"
                   % (stem, a.texture_sh ** 2, a.texture_sh))
     if compare:
-        full = extract_surface(model, normals=False, colors=True, **kw) if a.simplify > 0 else m
+        full = surface(model, normals=False, colors=True, **kw) if a.simplify > 0 else m
         renders = [("textured mesh", m, True, None), ("vertex-coloured mesh", m, False, None),
                    ("full-resolution vertex-coloured mesh", full, False, None)]
         if a.texture_sh > 0:  # the first line stays the flat atlas, baked for the check; the fourth is the SH atlas
