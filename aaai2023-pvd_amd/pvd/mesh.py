@@ -1531,3 +1531,90 @@ def extract_surface_tsdf(model, poses=None, intrinsics=None, H=400, W=400, resol
     extra = dict(field=field, threshold=0.0, counts=counts, tsdf_totals=totals, views=acc.views)
     return _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, extra, smooth, smooth_lambda, smooth_mu, simplify, clean,
                            min_shell_triangles, largest_shell_only, texture, texture_sh)
+
+
+# ------------------------------------------------------------------------------- image projection (csrc/pvd_hip_mesh_project.h)
+@torch.no_grad()
+def project_views(points, normals, vertices, triangles, color, poses, intrinsics, weight=None, cos_min=0.2, power=2, bias=None,
+                  sides="front", mode="blend", min_weight=1e-6, fallback=None, views_per_batch=16, grid=None, _grid=None):
+    """dict(colors [N,3] f32 in [0,1], seen [N] bool, weight [N] f32, totals dict(seen, unseen)), device tensors: the colour of every
+    surface point (points [N,3] with normals [N,3] of any length) from the posed images color [V,H,W,3] -- poses [V,4,4] cam2world as
+    get_rays takes them, intrinsics (fx, fy, cx, cy) for all views or [V,4], weight [V,H,W] optional (a confidence or opacity image; a
+    pixel of weight 0 shows nothing).  The standard photogrammetry step: a view counts for a point where it looks at the front of the
+    normal (sides="both": at either side) under a cosine above cos_min, the point projects between the centres of the outermost pixels,
+    the four pixels around it are finite, and no triangle of the mesh (vertices, triangles) lies between the point -- lifted by `bias`
+    along its normal, default 1e-3 of the diagonal of the finite vertices' box -- and the camera: an any-hit walk over mesh_raycast's grid
+    with its watertight test (csrc/pvd_hip_mesh_project.h has the definition to the operation; csrc/mesh_project.hip).  mode="blend":
+    the views are averaged with the weights cos^power times the bilinear weight; mode="best": the view of the largest weight alone.
+    A point whose weight stays below min_weight is unseen and gets `fallback` ([N,3], or a callable (points, unit normals) -> [M,3]
+    that is asked for the unseen points only; default 0).  The grid is built once (grid^3 cells, default default_grid(T)) and the views
+    are integrated views_per_batch at a time; neither changes a bit of the result.  `weight` in the dict is the accumulated weight.
+    Two read-backs: the grid's totals and the two totals of the result.  (_grid: (T, G, pairs, workspace, bias) of an earlier call's
+    _project_grid over the same mesh -- view_source builds it once for all the bands of a bake.)"""
+    import pvd_hip
+    dev = vertices.device
+    f = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=dev).contiguous()  # noqa: E731
+    points, normals = f(points).reshape(-1, 3), f(normals).reshape(-1, 3)
+    color, poses, weight = f(color), f(poses), f(weight)
+    N, V = int(points.shape[0]), int(color.shape[0])
+    intrinsics = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev)
+    if intrinsics.dim() == 1:
+        intrinsics = intrinsics[None, :].expand(V, 4)
+    intrinsics = intrinsics.contiguous()
+    T, G, pairs, ws, bias = _project_grid(vertices, triangles, grid, bias) if _grid is None else _grid
+    acc_c = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    acc_w = torch.zeros(N, dtype=torch.float32, device=dev)
+    step = max(int(views_per_batch), 1)
+    for s in range(0, max(V, 1), step):
+        pvd_hip.mesh_project_integrate(points, normals, color[s:s + step], None if weight is None else weight[s:s + step], poses[s:s + step],
+                                       intrinsics[s:s + step], T, G, pairs, ws, float(cos_min), int(power), float(bias), sides, mode, acc_c,
+                                       acc_w)
+    colors = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    if fallback is not None and not callable(fallback):
+        colors.copy_(f(fallback).reshape(N, 3))
+    seen = torch.empty(N, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    pvd_hip.mesh_project_finalize(acc_c, acc_w, float(min_weight), mode, colors, seen, totals)
+    seen = seen.bool()
+    totals = dict(zip(pvd_hip.MESH_PROJECT_TOTALS, (int(x) for x in totals.tolist())))
+    if callable(fallback) and totals["unseen"]:
+        rest = ~seen
+        colors[rest] = fallback(points[rest].contiguous(), _unit_rows(normals[rest]).contiguous()).to(torch.float32).reshape(-1, 3).clamp(0.0, 1.0)
+    return dict(colors=colors, seen=seen, weight=acc_w, totals=totals)
+
+
+def _project_grid(vertices, triangles, grid, bias):
+    """(T, G, pairs, workspace, bias): the ray grid of the mesh and the default bias, 1e-3 of the diagonal of the finite vertices' box"""
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    if bias is None:
+        lo, hi = _finite_box(vertices)
+        diag = float(torch.linalg.norm(hi - lo))
+        bias = 1e-3 * diag if diag == diag and diag < float("inf") else 0.0
+    return _ray_grid(vertices, triangles, None, None, grid) + (float(bias),)
+
+
+def _view_fallback(fallback):
+    """a model -> its colour head seen straight on (vertex_colors); a callable or None as it is"""
+    if fallback is not None and hasattr(fallback, "aabb_infer"):
+        model = fallback
+        return lambda x, n: vertex_colors(model, x, n)
+    return fallback
+
+
+def view_source(vertices, triangles, color, poses, intrinsics, fallback=None, **kw):
+    """A callable (x [M,3], n_unit [M,3]) -> rgb [M,3] for bake_texture: project_views of the images onto the points it is asked for,
+    over the mesh (vertices, triangles); kw: project_views' keywords.  fallback: a model (vertex_colors, the colour head seen straight
+    on) or a callable (x, n_unit) -> rgb, asked where no view sees the point; without one the colour is 0.
+    bake_texture(view_source(...), vertices, triangles, S) bakes the atlas from the images; the ray grid is built here, once."""
+    fallback = _view_fallback(fallback)
+    built = _project_grid(vertices, triangles, kw.pop("grid", None), kw.pop("bias", None))  # once for every band of the bake
+
+    def source(x, n):
+        return project_views(x, n, vertices, triangles, color, poses, intrinsics, fallback=fallback, _grid=built, **kw)["colors"]
+    return source
+
+
+def view_vertex_colors(vertices, triangles, normals, color, poses, intrinsics, fallback=None, **kw):
+    """[V,3] f32 in [0,1] on the device: project_views at the vertices with the vertex normals [V,3] (extract_mesh's, or
+    face_vertex_normals); fallback and kw as in view_source."""
+    return project_views(vertices, normals, vertices, triangles, color, poses, intrinsics, fallback=_view_fallback(fallback), **kw)["colors"]

@@ -124,13 +124,15 @@ ENTRY_POINTS_MESH_EXPOSE = ("pvd_mesh_expose",)
 ENTRY_POINTS_MESH_SHTEX = ("pvd_mesh_shtex_basis", "pvd_mesh_shtex_dirs", "pvd_mesh_shtex_project", "pvd_mesh_shtex_sample")
 # ... and the depth-map fusion of csrc/pvd_hip_mesh_tsdf.h (tests/test_abi_mesh_tsdf.py)
 ENTRY_POINTS_MESH_TSDF = ("pvd_mesh_tsdf_integrate", "pvd_mesh_tsdf_finalize", "pvd_mesh_tsdf_sample_color")
+# ... and the projection of posed images onto surface points of csrc/pvd_hip_mesh_project.h (tests/test_abi_mesh_project.py)
+ENTRY_POINTS_MESH_PROJECT = ("pvd_mesh_project_integrate", "pvd_mesh_project_finalize")
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
               + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING + ENTRY_POINTS_MESH_TEX
-              + ENTRY_POINTS_MESH_EXPOSE + ENTRY_POINTS_MESH_SHTEX + ENTRY_POINTS_MESH_TSDF):
+              + ENTRY_POINTS_MESH_EXPOSE + ENTRY_POINTS_MESH_SHTEX + ENTRY_POINTS_MESH_TSDF + ENTRY_POINTS_MESH_PROJECT):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -2242,6 +2244,81 @@ def mesh_tsdf_sample_color(acc_c, acc_w, R, bmin, bmax, min_weight, points, colo
         raise PvdHipError("colors must hold 3 N values, acc_c 3 R^3, acc_w R^3, bmin / bmax 3")
     _call("pvd_mesh_tsdf_sample_color", dev, _p(acc_c), _p(acc_w), _u32(R), _p(bmin), _p(bmax), ctypes.c_float(min_weight), _p(points), _u32(N),
           _p(colors))
+
+
+# --------------------------------------------------------------------------- image projection (csrc/pvd_hip_mesh_project.h)
+MESH_PROJECT_MAX_SIDE = 16384  # PVD_MESH_PROJECT_MAX_SIDE: the height and width of an image, 2 .. 16384
+MESH_PROJECT_MAX_POWER = 8  # PVD_MESH_PROJECT_MAX_POWER: the exponent of the facing cosine, 0 .. 8
+MESH_PROJECT_SIDES = ("front", "both")  # PVD_MESH_PROJECT_SIDES_FRONT = 0, _BOTH = 1
+MESH_PROJECT_MODES = ("blend", "best")  # PVD_MESH_PROJECT_MODE_BLEND = 0, _BEST = 1
+MESH_PROJECT_TOTALS = ("seen", "unseen")  # the two totals of mesh_project_finalize
+
+
+def _project_code(value, names, what):
+    if value not in names:
+        raise PvdHipError("%s must be one of %s, got %r" % (what, " / ".join(names), value))
+    return names.index(value)
+
+
+def mesh_project_integrate(points, normals, color, weight, poses, intrinsics, T, G, pairs, workspace, cos_min, power, bias, sides, mode,
+                           acc_c, acc_w):
+    """pvd_mesh_project_integrate: acc_c [N,3] f32 and acc_w [N] f32 (zeroed by the caller before the first call) += the views color
+    [V,H,W,3] f32 with weight [V,H,W] f32 or None, poses [V,4,4] f32 (cam2world, get_rays' convention) and intrinsics [V,4] f32 (fx, fy,
+    cx, cy), projected onto points [N,3] f32 with normals [N,3] f32 (any length): a view counts where it is in front of the point's
+    normal (sides "front"; "both": of either side) by more than cos_min, the point projects between the centres of its outermost
+    pixels, the four pixels around it are finite and no triangle of the mesh mesh_ray_build left in the workspace (the SAME T, G, pairs)
+    lies between the point, lifted by bias along its normal, and the camera; its weight is cos^power times the bilinear weight.
+    mode "blend" sums w and w rgb; "best" keeps the view of the largest w."""
+    dev = _dev(points, normals, color, weight, poses, intrinsics, workspace, acc_c, acc_w)
+    _f32_all(points=points, normals=normals, color=color, poses=poses, intrinsics=intrinsics, acc_c=acc_c, acc_w=acc_w)
+    if points.dim() != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+        raise PvdHipError("points and normals must be [N,3]")
+    N = int(points.shape[0])
+    if color.dim() != 4 or color.shape[3] != 3:
+        raise PvdHipError("color must be [V,H,W,3]")
+    V, H, W = (int(v) for v in color.shape[:3])
+    if not (2 <= H <= MESH_PROJECT_MAX_SIDE and 2 <= W <= MESH_PROJECT_MAX_SIDE):
+        raise PvdHipError("H and W must be 2 .. %d, got %d x %d" % (MESH_PROJECT_MAX_SIDE, H, W))
+    if tuple(poses.shape) != (V, 4, 4) or tuple(intrinsics.shape) != (V, 4):
+        raise PvdHipError("poses must be [V,4,4] and intrinsics [V,4] for V = %d" % V)
+    if weight is not None:
+        _f32_all(weight=weight)
+        if tuple(weight.shape) != (V, H, W):
+            raise PvdHipError("weight must be [V,H,W]")
+    if acc_c.numel() != 3 * N or acc_w.numel() != N:
+        raise PvdHipError("acc_c must hold 3 N values and acc_w N")
+    cos_min, bias, power = float(cos_min), float(bias), int(power)
+    if not 0.0 <= cos_min < 1.0:
+        raise PvdHipError("cos_min must be in [0, 1), got %r" % cos_min)
+    if not 0.0 <= bias < float("inf"):
+        raise PvdHipError("bias must be finite and not negative, got %r" % bias)
+    if not 0 <= power <= MESH_PROJECT_MAX_POWER:
+        raise PvdHipError("power must be 0 .. %d, got %d" % (MESH_PROJECT_MAX_POWER, power))
+    sides, mode = _project_code(sides, MESH_PROJECT_SIDES, "sides"), _project_code(mode, MESH_PROJECT_MODES, "mode")
+    _mesh_workspace(workspace, mesh_ray_workspace_bytes(T, G, pairs), "mesh_ray_workspace_bytes(T, G, pairs)")
+    _call("pvd_mesh_project_integrate", dev, _p(points), _p(normals), _u32(N), _p(color), _p(weight), _p(poses), _p(intrinsics), _u32(V),
+          _u32(H), _u32(W), _u32(T), _u32(G), _u64(pairs), _p(workspace), ctypes.c_size_t(workspace.numel()), _f32(cos_min), _u32(power),
+          _f32(bias), _u32(sides), _u32(mode), _p(acc_c), _p(acc_w))
+
+
+def mesh_project_finalize(acc_c, acc_w, min_weight, mode, colors, seen, totals):
+    """pvd_mesh_project_finalize: where acc_w >= min_weight, colors [N,3] f32 <- clamp(acc_c / acc_w, 0, 1) (mode "blend") or
+    clamp(acc_c, 0, 1) ("best") and seen [N] uint8 <- 1; elsewhere colors keeps what the caller put there (the fallback) and seen <- 0;
+    totals int64 [2] on the device <- MESH_PROJECT_TOTALS."""
+    dev = _dev(acc_c, acc_w, colors, seen, totals)
+    _f32_all(acc_c=acc_c, acc_w=acc_w, colors=colors)
+    _want(seen, torch.uint8, "seen")
+    _want(totals, torch.int64, "totals")
+    N = int(acc_w.numel())
+    if acc_c.numel() != 3 * N or colors.numel() != 3 * N or seen.numel() != N or totals.numel() < 2:
+        raise PvdHipError("acc_c and colors must hold 3 N values, seen N and totals 2")
+    min_weight = float(min_weight)
+    if not (0.0 < min_weight < float("inf")):
+        raise PvdHipError("min_weight must be positive and finite, got %r" % min_weight)
+    mode = _project_code(mode, MESH_PROJECT_MODES, "mode")
+    if N == 0:
+        totals[:2] = 0
+    _call("pvd_mesh_project_finalize", dev, _p(acc_c), _p(acc_w), _u32(N), _f32(min_weight), _u32(mode), _p(colors), _p(seen), _p(totals))
 
 
 # --------------------------------------------------------------------------- Taubin smoothing (include/pvd_hip_mesh_smooth.h)

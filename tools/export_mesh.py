@@ -61,7 +61,15 @@ default 3) and its zero level is meshed (extract_surface_tsdf).  No density thre
 carved empty, and --colors are the fused colours of the views -- except with --cull-hidden, which takes the colours after the cull, from
 the model's colour head at the vertices that are left, as it does without --tsdf (textures are always baked from the model).  Every other
 flag works as before, on that mesh; --threshold is ignored.
-With --render-check the line's mean |depth difference| then measures the fused surface against the model's own composited depth."""
+With --render-check the line's mean |depth difference| then measures the fused surface against the model's own composited depth.
+
+--project-views N [--project-size HW] [--project-best]: the vertex colours (--colors) and the atlas (--texture S) are taken from N
+rendered views (tsdf_poses; the colour maps of render_depth_maps, weighted by the opacity) projected onto the mesh with an occlusion
+test (pvd/mesh.py: project_views; csrc/mesh_project.hip), blended by cos^2 times the opacity or, with --project-best, taken from the
+best view; the model's colour head seen straight on is only the fallback where no view sees a point.  --render-check reports its usual
+lines, so the two bakes can be compared.  (With --simplify the third line's full-resolution mesh keeps the colour head's colours.)
+--project-data DIR [--project-split train] [--project-downscale K] projects the photographs of a Blender-format scene with their own
+poses (pvd.provider.BlenderScene) instead of renders; an alpha channel is the weight image."""
 import argparse
 import json
 import os
@@ -156,13 +164,63 @@ def cull_surface(model, m, mode, n_dirs=64, samples=1, colors=False, texture=0, 
     return report
 
 
+def load_view_data(root, split="train", downscale=1, device="cpu"):
+    """--project-data DIR: dict(color [V,H,W,3], weight [V,H,W] or None, poses [V,4,4], intrinsics (fx, fy, cx, cy), H, W) of a
+    Blender-format scene (transforms_<split>.json and its frames) through pvd.provider.BlenderScene: the photographs and their exact
+    poses, in the model's frame (nerf_matrix_to_ngp at the provider's scale).  An alpha channel becomes the weight image -- a
+    transparent pixel shows nothing of the surface -- and the colours are un-premultiplied as stored (PNG stores straight alpha)."""
+    from pvd.provider import BlenderScene
+    scene = BlenderScene(root, split=split, downscale=int(downscale), device=device, preload=True)
+    images = scene.images.float()
+    weight = images[..., 3].contiguous() if images.shape[-1] == 4 else None
+    return dict(color=images[..., :3].contiguous(), weight=weight, poses=scene.poses.float(), intrinsics=tuple(float(v) for v in scene.intrinsics),
+                H=int(scene.H), W=int(scene.W))
+
+
+@torch.no_grad()
+def project_surface(model, m, n_views, size=400, best=False, colors=True, texture=0, min_opacity=0.5, views=None):
+    """--project-views N: the colours of extract_surface's dict m from what the model RENDERS, not from its colour head seen straight
+    on: N tsdf_poses views of size x size are rendered (render_depth_maps: colour maps, and the opacity as the weight image, 0 below
+    min_opacity) and projected onto the mesh (pvd/mesh.py: project_views, csrc/mesh_project.hip) -- the vertex colours (colors), and with
+    texture=S the atlas through bake_texture(view_source(...)).  views: load_view_data's dict instead (--project-data): photographs.
+    Where no view sees a point the model's own colour is the fallback.  Needs m["normals"].  Leaves m["project_seen"] [V] bool with the
+    colours and returns dict(views, size, mode, vertices_seen, vertices_unseen)."""
+    import math
+    from pvd.mesh import project_views, render_depth_maps, vertex_colors, view_source
+    dev = m["vertices"].device
+    if views is None:
+        poses = tsdf_poses(int(n_views)).to(dev)
+        focal = 0.5 * size / math.tan(math.radians(25.0))
+        intr = (focal, focal, 0.5 * size, 0.5 * size)
+        maps = render_depth_maps(model, poses, intr, size, size, min_opacity=min_opacity)
+        color = maps["color"]
+        weight = torch.where(maps["opacity"] >= float(min_opacity), maps["opacity"], torch.zeros_like(maps["opacity"]))
+        shape = [int(size), int(size)]
+    else:
+        color, weight, poses, intr = views["color"].to(dev), views["weight"], views["poses"].to(dev), views["intrinsics"]
+        weight = None if weight is None else weight.to(dev)
+        shape = [int(views["H"]), int(views["W"])]
+    kw = dict(weight=weight, mode="best" if best else "blend")
+    own = lambda x, n: vertex_colors(model, x, n)  # noqa: E731
+    report = dict(views=int(color.shape[0]), size=shape[0] if shape[0] == shape[1] else shape, mode=kw["mode"])
+    if colors:
+        out = project_views(m["vertices"], m["normals"], m["vertices"], m["triangles"], color, poses, intr, fallback=own, **kw)
+        m["colors"], m["project_seen"] = out["colors"], out["seen"]
+        report.update(vertices_seen=out["totals"]["seen"], vertices_unseen=out["totals"]["unseen"])
+    if int(texture) > 0:
+        baked = bake_texture(view_source(m["vertices"], m["triangles"], color, poses, intr, fallback=own, **kw), m["vertices"],
+                             m["triangles"], int(texture), normals=m["normals"])
+        m.update(texture=baked["texture"], uv=baked["uv"], texture_cell=int(texture))
+    return report
+
+
 def enclosed_volume(vertices, triangles):
     """The volume a closed mesh encloses: the sum of the signed tetrahedra (origin, a, b, c), float64 in torch."""
     c = vertices.to(torch.float64)[triangles.to(torch.int64)]  # [T,3,3]
     return float((c[:, 0] * torch.linalg.cross(c[:, 1], c[:, 2])).sum() / 6.0)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoint")
     ap.add_argument("-o", "--out", default=None, help="PLY path (default: the checkpoint's name with .ply)")
@@ -200,7 +258,26 @@ def main():
     ap.add_argument("--tsdf", type=int, default=0, metavar="N", help="fuse the model's depth maps from N views into a TSDF volume and mesh its zero level")
     ap.add_argument("--tsdf-res", default="400x400", metavar="HxW", help="with --tsdf: the size of the rendered depth maps")
     ap.add_argument("--tsdf-trunc", type=float, default=3.0, metavar="K", help="with --tsdf: the truncation distance in lattice spacings")
-    a = ap.parse_args()
+    ap.add_argument("--project-views", type=int, default=0, metavar="N",
+                    help="colour the mesh (--colors, --texture) from N rendered views projected onto it, occlusion-tested, not from the colour head")
+    ap.add_argument("--project-size", type=int, default=400, metavar="HW", help="with --project-views: the side of the rendered views")
+    ap.add_argument("--project-best", action="store_true", help="with --project-views: take the best view per point instead of blending")
+    ap.add_argument("--project-data", default=None, metavar="DIR",
+                    help="project the photographs of a Blender-format scene (transforms_<split>.json, read through pvd.provider) instead of renders")
+    ap.add_argument("--project-split", default="train", help="with --project-data: train, val, test, trainval or all")
+    ap.add_argument("--project-downscale", type=int, default=1, metavar="K", help="with --project-data: read the photographs at 1 / K of their size")
+    a = ap.parse_args(argv)
+    projecting = a.project_views > 0 or a.project_data is not None
+    if a.project_views < 0 or (a.project_views > 0 and a.project_data is not None):
+        ap.error("--project-views N must not be negative, and it is either N rendered views or --project-data DIR")
+    if a.project_views == 0 and a.project_size != 400:
+        ap.error("--project-size needs --project-views N, N > 0")
+    if not projecting and a.project_best:
+        ap.error("--project-best needs --project-views N or --project-data DIR")
+    if a.project_data is None and (a.project_split != "train" or a.project_downscale != 1):
+        ap.error("--project-split and --project-downscale need --project-data DIR")
+    if projecting and (a.texture_sh > 0 or a.cull_hidden or not (a.colors or a.texture > 0) or a.project_size < 2 or a.project_downscale < 1):
+        ap.error("projection needs --colors or --texture, a size of at least 2, and goes with neither --texture-sh nor --cull-hidden")
     if a.tsdf < 0:
         ap.error("--tsdf N: the number of views must not be negative")
     if a.tsdf == 0 and (a.tsdf_res != "400x400" or a.tsdf_trunc != 3.0):
@@ -248,9 +325,20 @@ def main():
         exposure = cull_surface(model, m, a.cull_hidden, a.exposure_dirs, a.exposure_samples, colors=a.colors or compare, texture=a.texture,
                                 from_faces=a.smooth > 0, texture_sh=a.texture_sh)
     else:
-        m = surface(model, normals=a.normals, colors=a.colors or compare, simplify=a.simplify,
-                    **(dict(texture=a.texture) if a.texture > 0 else {}), **(dict(texture_sh=a.texture_sh) if a.texture_sh > 0 else {}),
-                    **kw)
+        # (with a projection the colours and the atlas come from the views below: the model's own are not taken first)
+        m = surface(model, normals=a.normals or projecting, colors=(a.colors or compare) and not projecting, simplify=a.simplify,
+                    **(dict(texture=a.texture) if a.texture > 0 and not projecting else {}),
+                    **(dict(texture_sh=a.texture_sh) if a.texture_sh > 0 else {}), **kw)
+    if projecting:  # the colours and the atlas from views projected onto the mesh; the model's own colour is only the fallback
+        if m["normals"] is None:  # (a surface function that returned none)
+            from pvd.mesh import face_vertex_normals
+            m["normals"] = face_vertex_normals(m["vertices"], m["triangles"])
+        views = None if a.project_data is None else load_view_data(a.project_data, a.project_split, a.project_downscale, dev)
+        projected = project_surface(model, m, a.project_views, a.project_size, a.project_best, colors=a.colors or compare, texture=a.texture,
+                                    views=views)
+        print("projected %d views at %s (%s)%s: %s" % (projected["views"], projected["size"], projected["mode"],
+                                                      "" if views is None else " from " + a.project_data,
+                                                      json.dumps({k: v for k, v in projected.items() if k.startswith("vertices")})))
     out = a.out or os.path.splitext(a.checkpoint)[0] + ".ply"
     write_ply(out, m["vertices"], m["triangles"], normals=m["normals"] if a.normals else None, colors=m["colors"] if a.colors else None)
     carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
