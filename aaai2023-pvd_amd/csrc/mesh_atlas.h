@@ -13,6 +13,48 @@ struct __attribute__((packed, aligned(4))) F3 {  // three floats moved as one 12
     float x, y, z;
 };
 
+PVD_HD float mix3(float wa, float wb, float wc, float a, float b, float c) {
+#pragma clang fp contract(off)
+    return (wa * a + wb * b) + wc * c;
+}
+
+// The point X and the normal N of the texel (p, q) of triangle f at the cell edge S ("Weights", "Point", "Normal", "Invalid" of the
+// header): six NaNs for an invalid triangle.  f < T is the caller's; k_mt_points and k_ax_points (csrc/mesh_atex.hip) share this.
+__device__ __forceinline__ void texel_point(const float *__restrict__ vertices, uint32_t V, const int32_t *__restrict__ triangles,
+                                            const float *__restrict__ normals, uint32_t f, uint32_t p, uint32_t q, uint32_t S, F3 &X,
+                                            F3 &N) {
+#pragma clang fp contract(off)
+    const float nan = u2f(0x7fc00000u);
+    X = {nan, nan, nan};
+    N = {nan, nan, nan};
+    const int32_t ia = triangles[3 * (size_t)f], ib = triangles[3 * (size_t)f + 1], ic = triangles[3 * (size_t)f + 2];
+    if (!((uint32_t)ia < V && (uint32_t)ib < V && (uint32_t)ic < V)) return;  // a negative index is a large unsigned one
+    const float *pa = vertices + 3 * (size_t)ia, *pb = vertices + 3 * (size_t)ib, *pc = vertices + 3 * (size_t)ic;
+    const float ax = pa[0], ay = pa[1], az = pa[2], bx = pb[0], by = pb[1], bz = pb[2], gx = pc[0], gy = pc[1], gz = pc[2];
+    bool ok = finite3(ax, ay, az) && finite3(bx, by, bz) && finite3(gx, gy, gz);
+    const float m = (float)(S - 3);
+    const float beta = (float)p / m, gamma = (float)q / m;
+    const float alpha = (1.0f - beta) - gamma;
+    float nx, ny, nz;
+    if (normals) {
+        const float *na = normals + 3 * (size_t)ia, *nb = normals + 3 * (size_t)ib, *nc = normals + 3 * (size_t)ic;
+        const float a0 = na[0], a1 = na[1], a2 = na[2], b0 = nb[0], b1 = nb[1], b2 = nb[2], c0 = nc[0], c1 = nc[1], c2 = nc[2];
+        ok = ok && finite3(a0, a1, a2) && finite3(b0, b1, b2) && finite3(c0, c1, c2);
+        nx = mix3(alpha, beta, gamma, a0, b0, c0);
+        ny = mix3(alpha, beta, gamma, a1, b1, c1);
+        nz = mix3(alpha, beta, gamma, a2, b2, c2);
+    } else {
+        const float ux = bx - ax, uy = by - ay, uz = bz - az, vx = gx - ax, vy = gy - ay, vz = gz - az;
+        nx = uy * vz - uz * vy;
+        ny = uz * vx - ux * vz;
+        nz = ux * vy - uy * vx;
+    }
+    if (ok) {
+        X = {mix3(alpha, beta, gamma, ax, bx, gx), mix3(alpha, beta, gamma, ay, by, gy), mix3(alpha, beta, gamma, az, bz, gz)};
+        N = {nx, ny, nz};
+    }
+}
+
 // fu, i0, tx of the header from one weight
 __device__ __forceinline__ void texel_of(float w, uint32_t mi, uint32_t &i0, float &t) {
 #pragma clang fp contract(off)

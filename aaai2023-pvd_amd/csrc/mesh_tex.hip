@@ -47,11 +47,6 @@ int layout_of(uint32_t T, uint32_t S, TexLayout &l) {
     return PVD_OK;
 }
 
-PVD_HD float mix3(float wa, float wb, float wc, float a, float b, float c) {
-#pragma clang fp contract(off)
-    return (wa * a + wb * b) + wc * c;
-}
-
 __global__ __launch_bounds__(kThreads) void k_mt_points(const float *__restrict__ vertices, uint32_t V, const int32_t *__restrict__ triangles,
                                                        uint32_t T, const float *__restrict__ normals, uint32_t S, uint32_t C, uint32_t Wt,
                                                        uint32_t row0, F3 *__restrict__ out_x, F3 *__restrict__ out_n) {
@@ -66,35 +61,7 @@ __global__ __launch_bounds__(kThreads) void k_mt_points(const float *__restrict_
     const uint32_t p = lower ? i : S - 1 - i, q = lower ? j : S - 1 - j;
     const float nan = u2f(0x7fc00000u);
     F3 X = {nan, nan, nan}, N = {nan, nan, nan};
-    if (f < T) {
-        const int32_t ia = triangles[3 * (size_t)f], ib = triangles[3 * (size_t)f + 1], ic = triangles[3 * (size_t)f + 2];
-        if ((uint32_t)ia < V && (uint32_t)ib < V && (uint32_t)ic < V) {  // a negative index is a large unsigned one
-            const float *pa = vertices + 3 * (size_t)ia, *pb = vertices + 3 * (size_t)ib, *pc = vertices + 3 * (size_t)ic;
-            const float ax = pa[0], ay = pa[1], az = pa[2], bx = pb[0], by = pb[1], bz = pb[2], gx = pc[0], gy = pc[1], gz = pc[2];
-            bool ok = finite3(ax, ay, az) && finite3(bx, by, bz) && finite3(gx, gy, gz);
-            const float m = (float)(S - 3);
-            const float beta = (float)p / m, gamma = (float)q / m;
-            const float alpha = (1.0f - beta) - gamma;
-            float nx, ny, nz;
-            if (normals) {
-                const float *na = normals + 3 * (size_t)ia, *nb = normals + 3 * (size_t)ib, *nc = normals + 3 * (size_t)ic;
-                const float a0 = na[0], a1 = na[1], a2 = na[2], b0 = nb[0], b1 = nb[1], b2 = nb[2], c0 = nc[0], c1 = nc[1], c2 = nc[2];
-                ok = ok && finite3(a0, a1, a2) && finite3(b0, b1, b2) && finite3(c0, c1, c2);
-                nx = mix3(alpha, beta, gamma, a0, b0, c0);
-                ny = mix3(alpha, beta, gamma, a1, b1, c1);
-                nz = mix3(alpha, beta, gamma, a2, b2, c2);
-            } else {
-                const float ux = bx - ax, uy = by - ay, uz = bz - az, vx = gx - ax, vy = gy - ay, vz = gz - az;
-                nx = uy * vz - uz * vy;
-                ny = uz * vx - ux * vz;
-                nz = ux * vy - uy * vx;
-            }
-            if (ok) {
-                X = {mix3(alpha, beta, gamma, ax, bx, gx), mix3(alpha, beta, gamma, ay, by, gy), mix3(alpha, beta, gamma, az, bz, gz)};
-                N = {nx, ny, nz};
-            }
-        }
-    }
+    if (f < T) texel_point(vertices, V, triangles, normals, f, p, q, S, X, N);  // csrc/mesh_atlas.h
     const size_t e = (size_t)r * Wt + x;  // inside the band: r < row1 - row0, x < Wt
     out_x[e] = X;
     out_n[e] = N;

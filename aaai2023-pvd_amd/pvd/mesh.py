@@ -172,7 +172,7 @@ def vertex_colors(model, vertices, normals, chunk=1 << 20, autocast=True):
 
 def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, min_points=0, largest_only=False,
                     normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, clean=False,
-                    min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0):
+                    min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0, texture_density=0.0):
     """extract_geometry with what a viewer needs next to the geometry, as a dict: vertices, triangles, normals (extract_mesh's
     with_normals) and colors (vertex_colors), None where not asked for; field (the density volume, filtered where min_points > 0
     or largest_only), threshold, and counts = (components found, components kept, points kept), None where nothing was filtered.
@@ -192,7 +192,10 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
     texture=0: the dict is what it was.
     texture_sh=L > 0 with texture=S > 0: bake_sh_texture (L bands of spherical harmonics per texel, the colour as a function of the
     view) in place of the flat bake; the dict then holds texture [Ht,Wt,L*L,3], texture_degree = L and texture_diffuse [Ht,Wt,3], the
-    view-independent part, next to uv and texture_cell.  texture_sh=0: the dict is what it was."""
+    view-independent part, next to uv and texture_cell.  texture_sh=0: the dict is what it was.
+    texture_density=D > 0: the flat bake goes onto an area-adaptive atlas (adaptive_atlas: D texels per unit length, a cell edge per
+    triangle, at most texture=S where given and 64 otherwise); texture_cell is then that atlas.  With texture_sh it raises ValueError.
+    texture_density=0: the dict is what it was."""
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -211,11 +214,11 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
     else:
         vertices, triangles = extract_mesh(u, threshold, lo, hi)
     return _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, dict(field=u, threshold=float(threshold), counts=counts),
-                           smooth, smooth_lambda, smooth_mu, simplify, clean, min_shell_triangles, largest_shell_only, texture, texture_sh)
+                           smooth, smooth_lambda, smooth_mu, simplify, clean, min_shell_triangles, largest_shell_only, texture, texture_sh, texture_density)
 
 
 def _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, extra, smooth, smooth_lambda, smooth_mu, simplify, clean,
-                    min_shell_triangles, largest_shell_only, texture, texture_sh):
+                    min_shell_triangles, largest_shell_only, texture, texture_sh, texture_density=0.0):
     """The tail extract_surface and extract_surface_tsdf share: smoothing, the dict (with `extra` after the four mesh entries), the
     simplification, the clean-up and the texture bake, in extract_surface's order and with its meaning."""
     if int(smooth) > 0:
@@ -237,7 +240,13 @@ def _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, extra
             vmap = torch.where(first >= 0, vmap[first.clamp(min=0).long()], torch.full_like(first, -1))
         out.update(vertices=done["vertices"], triangles=done["triangles"], normals=done["normals"], colors=done["colors"],
                    vertex_map=vmap, triangle_map=done["triangle_map"], topology=dict(before=done["before"], after=done["after"]))
-    if int(texture) > 0 and int(texture_sh) > 0:
+    if float(texture_density) > 0.0:
+        if int(texture_sh) > 0:
+            raise ValueError("texture_sh needs a uniform atlas: texture_density (the adaptive atlas) is for flat textures only")
+        atlas = adaptive_atlas(out["vertices"], out["triangles"], float(texture_density), max_cell=int(texture) if int(texture) > 0 else 64)
+        baked = bake_texture(model, out["vertices"], out["triangles"], atlas, normals=out["normals"])
+        out.update(texture=baked["texture"], uv=baked["uv"], texture_cell=atlas)
+    elif int(texture) > 0 and int(texture_sh) > 0:
         baked = bake_sh_texture(model, out["vertices"], out["triangles"], int(texture), degree=int(texture_sh), normals=out["normals"])
         out.update(texture=baked["texture"], uv=baked["uv"], texture_cell=int(texture), texture_degree=int(texture_sh),
                    texture_diffuse=baked["diffuse"])
@@ -765,7 +774,8 @@ def render_mesh(vertices, triangles, pose, intrinsics, H, W, normals=None, color
     The interpolation is plain torch gathers on the cast's output.
     texture [Ht,Wt,3] with texture_cell = S (bake_texture's, for these triangles): color is sample_texture's bilinear lookup of the
     atlas at the hits instead (csrc/mesh_tex.hip), whatever colors holds.  A 4-D texture [Ht,Wt,K,3] (bake_sh_texture's) is an SH atlas:
-    color is sample_sh_texture's, evaluated at each ray's direction (csrc/mesh_shtex.hip); K gives the number of bands."""
+    color is sample_sh_texture's, evaluated at each ray's direction (csrc/mesh_shtex.hip); K gives the number of bands.
+    texture_cell = adaptive_atlas's dict (bake_texture returns it as texture_cell): the flat lookup on that atlas (csrc/mesh_atex.hip)."""
     from .scene import get_rays
     dev = vertices.device
     pose = torch.as_tensor(pose, dtype=torch.float32, device=dev).reshape(4, 4)
@@ -954,19 +964,74 @@ def _volume_overlap(va, ta, vb, tb, R):
 
 
 # ------------------------------------------------------------------------------------------------ texture atlases
+def _is_atlas(S):
+    """True for adaptive_atlas's dict where the texture functions take the cell edge S."""
+    return isinstance(S, dict) and "slot" in S and "order" in S and "counts" in S
+
+
+def _atlas_for(S, T):
+    if int(S["triangles"]) != int(T):
+        raise ValueError("the adaptive atlas was built for %d triangles, the mesh has %d" % (int(S["triangles"]), int(T)))
+    return S
+
+
+def adaptive_atlas(vertices, triangles, density, max_cell=64):
+    """The area-adaptive atlas of csrc/pvd_hip_mesh_atex.h for the mesh: every triangle gets the smallest cell edge of 4, 8, 16, 32, 64
+    texels (at most max_cell) that gives it `density` texels per unit length along its longest edge, and the triangles of one cell size
+    are packed into one band of the image in the order of their index (csrc/mesh_atex.hip: a counting sort by scans, no atomics, the
+    same bits every run).  A dict: slot [T] int32 (class << 28 | rank) and order [T] int32 on the device, counts (five integers),
+    capped (triangles that needed more than max_cell), density, triangles = T and layout = dict(width, height, y0, rows, cells_per_row,
+    cell: five numbers each, triangles).  texture_layout, texture_uv, texture_points, bake_texture, sample_texture and
+    render_mesh(texture_cell=...) take it in place of the integer S."""
+    import pvd_hip
+    if int(max_cell) not in pvd_hip.MESH_ATEX_CELLS:
+        raise ValueError("max_cell must be one of %s, got %r" % (pvd_hip.MESH_ATEX_CELLS, max_cell))
+    if not float(density) > 0.0 or float(density) == float("inf"):
+        raise ValueError("density must be positive and finite, got %r" % (density,))
+    vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+    triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    dev, T = vertices.device, int(triangles.shape[0])
+    slot = torch.empty(T, dtype=torch.int32, device=dev)
+    order = torch.empty(T, dtype=torch.int32, device=dev)
+    totals = torch.zeros(6, dtype=torch.int32, device=dev)
+    ws = torch.empty(pvd_hip.mesh_atex_workspace_bytes(T), dtype=torch.uint8, device=dev)
+    pvd_hip.mesh_atex_build(vertices, triangles, float(density), pvd_hip.MESH_ATEX_CELLS.index(int(max_cell)), ws, slot, order, totals)
+    totals = [int(v) for v in totals.tolist()]
+    counts = tuple(totals[:5])
+    Wt, Ht, y0, rows, C = pvd_hip.mesh_atex_layout(counts)
+    return dict(slot=slot, order=order, counts=counts, capped=totals[5], density=float(density), triangles=T,
+                layout=dict(width=Wt, height=Ht, y0=y0, rows=rows, cells_per_row=C, cell=tuple(pvd_hip.MESH_ATEX_CELLS), triangles=T))
+
+
 def texture_layout(T, S):
     """dict(cells_per_row, rows, width, height, cell, triangles) of the per-triangle atlas of include/pvd_hip_mesh_tex.h: two triangles
     share a square cell of S x S texels (S 4 .. 64), C cells per row with C the smallest integer whose square holds ceil(T / 2) cells.
-    A side above 16384 texels raises."""
+    A side above 16384 texels raises.  S = adaptive_atlas's dict: its layout (width, height, and per class y0, rows, cells_per_row, cell)."""
     import pvd_hip
+    if _is_atlas(S):
+        return dict(_atlas_for(S, T)["layout"])
     C, rows, Wt, Ht = pvd_hip.mesh_tex_layout(int(T), int(S))
     return dict(cells_per_row=C, rows=rows, width=Wt, height=Ht, cell=int(S), triangles=int(T))
 
 
 def texture_uv(T, S, device=None):
     """[T,3,2] f32: the texture coordinates of the three corners of every triangle in the OBJ convention (u to the right, v up, the
-    image's first row at v = 1): the centres of the texels that hold the corners' baked values.  The header's closed form, in torch."""
+    image's first row at v = 1): the centres of the texels that hold the corners' baked values.  The header's closed form, in torch
+    (with an adaptive atlas: per triangle from its slot, csrc/pvd_hip_mesh_atex.h)."""
     lay = texture_layout(T, S)
+    if _is_atlas(S):
+        slot = S["slot"].to(torch.int64) if device is None else S["slot"].to(device=device, dtype=torch.int64)
+        c, k = slot >> 28, (slot & 0x0fffffff) // 2
+        odd = (slot & 1) == 1
+        cell = torch.tensor(lay["cell"], dtype=torch.int64, device=slot.device)[c]
+        C = torch.tensor(lay["cells_per_row"], dtype=torch.int64, device=slot.device)[c]
+        y0 = torch.tensor(lay["y0"], dtype=torch.int64, device=slot.device)[c]
+        ax = (k % C) * cell + torch.where(odd, cell - 1, torch.zeros_like(cell))
+        ay = y0 + (k // C) * cell + torch.where(odd, cell - 1, torch.zeros_like(cell))
+        step = torch.where(odd, 3 - cell, cell - 3)
+        X = torch.stack([ax, ax + step, ax], dim=1).to(torch.float64) + 0.5
+        Y = torch.stack([ay, ay, ay + step], dim=1).to(torch.float64) + 0.5
+        return torch.stack([X / lay["width"], 1.0 - Y / lay["height"]], dim=2).to(torch.float32)
     C, Wt, Ht, S, m = lay["cells_per_row"], lay["width"], lay["height"], int(S), int(S) - 3
     f = torch.arange(int(T), dtype=torch.int64, device=device)
     k, odd = f // 2, (f % 2) == 1
@@ -982,7 +1047,8 @@ def texture_points(vertices, triangles, S, normals=None, rows=None):
     """(x, n) [(row1 - row0) * width, 3] f32 on the device: the surface point and the normal of every texel of the image rows
     rows = (row0, row1) (default: the whole atlas) of the mesh's atlas (csrc/mesh_tex.hip).  n: the weights of x on the vertex normals
     [V,3], left unnormalised, or the face normal without them.  Six NaNs for a texel nothing owns and for the texels of a triangle with an
-    index outside [0, V) or a corner (or given normal) that is not finite."""
+    index outside [0, V) or a corner (or given normal) that is not finite.  S = adaptive_atlas's dict: the same on that atlas
+    (csrc/mesh_atex.hip)."""
     import pvd_hip
     vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
     triangles = triangles.to(torch.int32).reshape(-1, 3).contiguous()
@@ -993,7 +1059,10 @@ def texture_points(vertices, triangles, S, normals=None, rows=None):
     count = max(row1 - row0, 0) * lay["width"]
     x = torch.empty(count, 3, dtype=torch.float32, device=vertices.device)
     n = torch.empty(count, 3, dtype=torch.float32, device=vertices.device)
-    pvd_hip.mesh_tex_points(vertices, triangles, normals, int(S), row0, row1, x, n)
+    if _is_atlas(S):
+        pvd_hip.mesh_atex_points(vertices, triangles, normals, S["counts"], S["order"], row0, row1, x, n)
+    else:
+        pvd_hip.mesh_tex_points(vertices, triangles, normals, int(S), row0, row1, x, n)
     return x, n
 
 
@@ -1008,7 +1077,9 @@ def bake_texture(source, vertices, triangles, S, normals=None, chunk=1 << 20):
     """dict(texture [Ht,Wt,3] f32 in [0,1], uv [T,3,2] f32, layout): the colour of `source` at the surface point of every texel of the
     mesh's atlas (texture_layout, texture_points).  source: a model -- vertex_colors(model, x, n / |n|), the colour head seen straight
     on, as the vertex colours are taken -- or a callable (x [M,3], n_unit [M,3]) -> [M,3].  Baked in bands of whole image rows of about
-    `chunk` texels; texels nothing owns, and those of invalid triangles, get the colour 0 and never reach the source."""
+    `chunk` texels; texels nothing owns, and those of invalid triangles, get the colour 0 and never reach the source.
+    S = adaptive_atlas's dict: the bake on that atlas; the dict then also holds texture_cell = the atlas, which is what sample_texture,
+    render_mesh and evaluate_mesh_views take in place of S."""
     T = int(triangles.reshape(-1, 3).shape[0])
     lay = texture_layout(T, S)
     Wt, Ht = lay["width"], lay["height"]
@@ -1026,13 +1097,17 @@ def bake_texture(source, vertices, triangles, S, normals=None, chunk=1 << 20):
             if bool(good.any()):
                 rgb[good] = source(x[good].contiguous(), _unit_rows(n[good]).contiguous()).to(torch.float32).reshape(-1, 3).clamp(0.0, 1.0)
         texture[row0:row1] = rgb.reshape(row1 - row0, Wt, 3)
-    return dict(texture=texture, uv=texture_uv(T, S, device=vertices.device), layout=lay)
+    out = dict(texture=texture, uv=texture_uv(T, S, device=vertices.device), layout=lay)
+    if _is_atlas(S):
+        out["texture_cell"] = S
+    return out
 
 
 def sample_texture(texture, S, T, tri, bary, bg_color=1.0):
     """[..., 3] f32 on the device: the bilinear lookup of texture [Ht,Wt,3] (the atlas of T triangles at the cell edge S) at the hits
     (tri [...] int32, bary [..., 2] f32) of mesh_raycast; bg_color (a float or 3 floats) where tri is -1.  Reads the hit triangle's own
-    cell only (include/pvd_hip_mesh_tex.h; csrc/mesh_tex.hip)."""
+    cell only (include/pvd_hip_mesh_tex.h; csrc/mesh_tex.hip).  S = adaptive_atlas's dict: the lookup on that atlas
+    (csrc/mesh_atex.hip)."""
     import pvd_hip
     dev = texture.device
     texture = texture.to(torch.float32).contiguous()
@@ -1041,7 +1116,10 @@ def sample_texture(texture, S, T, tri, bary, bg_color=1.0):
     bary = bary.to(torch.float32).reshape(-1, 2).contiguous()
     bg = torch.as_tensor(bg_color, dtype=torch.float32, device=dev).expand(3).contiguous()
     color = torch.empty(int(tri.shape[0]), 3, dtype=torch.float32, device=dev)
-    pvd_hip.mesh_tex_sample(texture, int(T), int(S), tri, bary, bg, color)
+    if _is_atlas(S):
+        pvd_hip.mesh_atex_sample(texture, int(T), _atlas_for(S, T)["counts"], S["slot"], tri, bary, bg, color)
+    else:
+        pvd_hip.mesh_tex_sample(texture, int(T), int(S), tri, bary, bg, color)
     return color.reshape(shape + (3,))
 
 
@@ -1270,6 +1348,11 @@ def _colors_along(model, x, d, chunk, autocast=True):
     return out
 
 
+def _no_sh_atlas(S):
+    if _is_atlas(S):
+        raise ValueError("SH atlases take an integer cell edge: the adaptive atlas (adaptive_atlas) is for flat textures only")
+
+
 @torch.no_grad()
 def bake_sh_texture(source, vertices, triangles, S, degree=3, dirs=None, normals=None, chunk=1 << 20, batch=8):
     """dict(texture [Ht,Wt,K,3] f32, uv [T,3,2] f32, layout, degree, diffuse [Ht,Wt,3] f32): per texel of the mesh's atlas
@@ -1283,6 +1366,7 @@ def bake_sh_texture(source, vertices, triangles, S, degree=3, dirs=None, normals
     diffuse = clamp(coef[..., 0, :] * Y_0, 0, 1), the view-independent part: what an OBJ / PNG can carry.  sample_sh_texture and
     render_mesh(texture=...) evaluate the atlas at a ray's direction."""
     import pvd_hip
+    _no_sh_atlas(S)
     L = _sh_bands(degree)
     K = L * L
     dev = vertices.device
@@ -1330,6 +1414,7 @@ def sample_sh_texture(texture, S, T, tri, bary, dirs, bg_color=1.0):
     import math
 
     import pvd_hip
+    _no_sh_atlas(S)
     if texture.dim() != 4:
         raise ValueError("an SH atlas is [Ht,Wt,K,3]")
     K = int(texture.shape[2])
@@ -1487,7 +1572,7 @@ def render_depth_maps(model, poses, intrinsics, H, W, min_opacity=0.5, free_opac
 def extract_surface_tsdf(model, poses=None, intrinsics=None, H=400, W=400, resolution=256, tau=None, bmin=None, bmax=None,
                          views_per_batch=8, min_weight=1.0, unknown=-1.0, min_opacity=0.5, free_opacity=0.05, min_points=0,
                          largest_only=False, normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53,
-                         clean=False, min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0):
+                         clean=False, min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0, texture_density=0.0):
     """extract_surface with the geometry taken from what the model RENDERS: depth and colour maps of `poses` (render_depth_maps;
     default tsdf_poses(), with intrinsics of a 50 degree field of view where none are given) are fused into a TSDFVolume over the box
     (default model.aabb_infer), views_per_batch at a time, and the zero level of tsdf_field is meshed -- where the model's rays end,
@@ -1495,7 +1580,7 @@ def extract_surface_tsdf(model, poses=None, intrinsics=None, H=400, W=400, resol
     vertices, triangles, normals (the gradient of the fused field: extract_mesh's with_normals), colors (tsdf_vertex_colors: the
     fused colours, no second pass over the model), field (the TSDF, positive outside), threshold = 0.0 and counts, plus tsdf_totals
     (tsdf_field's) and views.  min_points, largest_only, smooth, simplify, clean, texture and texture_sh mean exactly what they mean in
-    extract_surface and go through the same functions."""
+    extract_surface and go through the same functions, and so does texture_density."""
     import math
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
@@ -1530,7 +1615,7 @@ def extract_surface_tsdf(model, poses=None, intrinsics=None, H=400, W=400, resol
         vertices, triangles = extract_mesh(u, 0.0, lo, hi)
     extra = dict(field=field, threshold=0.0, counts=counts, tsdf_totals=totals, views=acc.views)
     return _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, extra, smooth, smooth_lambda, smooth_mu, simplify, clean,
-                           min_shell_triangles, largest_shell_only, texture, texture_sh)
+                           min_shell_triangles, largest_shell_only, texture, texture_sh, texture_density)
 
 
 # ------------------------------------------------------------------------------- image projection (csrc/pvd_hip_mesh_project.h)

@@ -126,13 +126,17 @@ ENTRY_POINTS_MESH_SHTEX = ("pvd_mesh_shtex_basis", "pvd_mesh_shtex_dirs", "pvd_m
 ENTRY_POINTS_MESH_TSDF = ("pvd_mesh_tsdf_integrate", "pvd_mesh_tsdf_finalize", "pvd_mesh_tsdf_sample_color")
 # ... and the projection of posed images onto surface points of csrc/pvd_hip_mesh_project.h (tests/test_abi_mesh_project.py)
 ENTRY_POINTS_MESH_PROJECT = ("pvd_mesh_project_integrate", "pvd_mesh_project_finalize")
+# ... and the area-adaptive texture atlas of csrc/pvd_hip_mesh_atex.h (tests/test_abi_mesh_atex.py)
+ENTRY_POINTS_MESH_ATEX = ("pvd_mesh_atex_workspace_bytes", "pvd_mesh_atex_build", "pvd_mesh_atex_layout", "pvd_mesh_atex_points",
+                          "pvd_mesh_atex_sample")
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
 for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POINTS_DATA + ENTRY_POINTS_MARCH + ENTRY_POINTS_MESH
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
               + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING + ENTRY_POINTS_MESH_TEX
-              + ENTRY_POINTS_MESH_EXPOSE + ENTRY_POINTS_MESH_SHTEX + ENTRY_POINTS_MESH_TSDF + ENTRY_POINTS_MESH_PROJECT):
+              + ENTRY_POINTS_MESH_EXPOSE + ENTRY_POINTS_MESH_SHTEX + ENTRY_POINTS_MESH_TSDF + ENTRY_POINTS_MESH_PROJECT
+              + ENTRY_POINTS_MESH_ATEX):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -150,6 +154,7 @@ _lib.pvd_mesh_ray_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_smooth_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_topo_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_winding_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_atex_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -2097,6 +2102,107 @@ def mesh_tex_sample(texture, T, S, tri, bary, bg3, color):
     if bary.numel() != 2 * N or color.numel() != 3 * N or bg3.numel() < 3:
         raise PvdHipError("bary must hold 2 N, color 3 N and bg3 3 values")
     _call("pvd_mesh_tex_sample", dev, _p(texture), _u32(T), _u32(S), _p(tri), _p(bary), _u32(N), _p(bg3), _p(color))
+
+
+# --------------------------------------------------------------------------- area-adaptive atlas (csrc/pvd_hip_mesh_atex.h)
+MESH_ATEX_CELLS = (4, 8, 16, 32, 64)  # the cell edge S_c of class c = 0 .. 4
+MESH_ATEX_TOTALS = ("count_0", "count_1", "count_2", "count_3", "count_4", "capped")  # the six totals of mesh_atex_build
+MESH_ATEX_MAX_T = 2 ** 28 - 1  # PVD_MESH_ATEX_MAX_T
+MESH_ATEX_MAX_SIDE = 16384  # PVD_MESH_ATEX_MAX_SIDE
+
+
+def mesh_atex_workspace_bytes(T):
+    """pvd_mesh_atex_workspace_bytes: bytes of workspace mesh_atex_build needs for T triangles."""
+    n = int(_lib.pvd_mesh_atex_workspace_bytes(_u32(T))) if 0 <= int(T) < 2 ** 32 else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_atex_workspace_bytes: T must be at most %d, got %d" % (MESH_ATEX_MAX_T, int(T)))
+    return n
+
+
+def _atex_counts(counts, T=None):
+    counts = tuple(int(c) for c in counts)
+    if len(counts) != 5 or any(not 0 <= c < 2 ** 32 for c in counts):
+        raise PvdHipError("counts must be five numbers in 0 .. 2^32 - 1 (the first five totals of mesh_atex_build)")
+    if T is not None and sum(counts) != int(T):
+        raise PvdHipError("counts must sum to T = %d, got %s" % (int(T), counts))
+    return counts, (ctypes.c_uint32 * 5)(*counts)
+
+
+def mesh_atex_layout(counts):
+    """pvd_mesh_atex_layout: (Wt, Ht, y0 [5], rows [5], C [5]) of the adaptive atlas with counts[c] triangles of class c (host only)."""
+    counts, arr = _atex_counts(counts)
+    out = (ctypes.c_uint32 * 17)()
+    if _lib.pvd_mesh_atex_layout(arr, out) != 0:
+        raise PvdHipError("pvd_mesh_atex_layout: at most %d triangles and no side of the atlas above %d, got counts=%s"
+                          % (MESH_ATEX_MAX_T, MESH_ATEX_MAX_SIDE, counts))
+    v = [int(x) for x in out]
+    return v[0], v[1], tuple(v[2:7]), tuple(v[7:12]), tuple(v[12:17])
+
+
+def mesh_atex_build(vertices, triangles, density, max_class, workspace, slot, order, totals):
+    """pvd_mesh_atex_build: slot [T] int32 (class << 28 | rank), order [T] int32 and totals int32 [6] (MESH_ATEX_TOTALS) on the device
+    <- the class of every triangle of the mesh (vertices [V,3] f32, triangles [T,3] int32) at `density` texels per unit length, capped at
+    max_class 0 .. 4, and its rank among the triangles of its class; workspace: uint8, mesh_atex_workspace_bytes(T).  No atomics."""
+    dev = _dev(vertices, triangles, workspace, slot, order, totals)
+    _f32_all(vertices=vertices)
+    for k, t in (("triangles", triangles), ("slot", slot), ("order", order), ("totals", totals)):
+        _want(t, torch.int32, k)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    if slot.numel() != T or order.numel() != T or totals.numel() < 6:
+        raise PvdHipError("slot and order must hold T values and totals 6")
+    if not 0 <= int(max_class) <= 4:
+        raise PvdHipError("max_class must be 0 .. 4, got %d" % int(max_class))
+    _mesh_workspace(workspace, mesh_atex_workspace_bytes(T), "mesh_atex_workspace_bytes(T)")
+    _call("pvd_mesh_atex_build", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _f32(density), _u32(max_class), _p(workspace),
+          ctypes.c_size_t(workspace.numel()), _p(slot), _p(order), _p(totals))
+
+
+def mesh_atex_points(vertices, triangles, normals, counts, order, row0, row1, x, n):
+    """pvd_mesh_atex_points: mesh_tex_points on the adaptive atlas: counts (five host integers) and order [T] int32 are
+    mesh_atex_build's."""
+    dev = _dev(vertices, triangles, normals, order, x, n)
+    _f32_all(vertices=vertices, x=x, n=n)
+    _want(triangles, torch.int32, "triangles")
+    _want(order, torch.int32, "order")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    if normals is not None:
+        _f32_all(normals=normals)
+        if normals.dim() != 2 or tuple(normals.shape) != (V, 3):
+            raise PvdHipError("normals must be [V,3]")
+    counts, arr = _atex_counts(counts, T)
+    if order.numel() != T:
+        raise PvdHipError("order must hold T values")
+    Wt, Ht = mesh_atex_layout(counts)[:2]
+    row0, row1 = int(row0), int(row1)
+    if not 0 <= row0 <= row1 <= Ht:
+        raise PvdHipError("rows must satisfy 0 <= row0 <= row1 <= %d, got %d, %d" % (Ht, row0, row1))
+    if x.numel() != (row1 - row0) * Wt * 3 or n.numel() != x.numel():
+        raise PvdHipError("x and n must hold (row1 - row0) * Wt * 3 values")
+    _call("pvd_mesh_atex_points", dev, _p(vertices), _u32(V), _p(triangles), _u32(T), _p(normals), arr, _p(order), _u32(row0),
+          _u32(row1), _p(x), _p(n))
+
+
+def mesh_atex_sample(texture, T, counts, slot, tri, bary, bg3, color):
+    """pvd_mesh_atex_sample: mesh_tex_sample on the adaptive atlas: counts (five host integers) and slot [T] int32 are
+    mesh_atex_build's."""
+    dev = _dev(texture, slot, tri, bary, bg3, color)
+    _f32_all(texture=texture, bary=bary, bg3=bg3, color=color)
+    _want(tri, torch.int32, "tri")
+    _want(slot, torch.int32, "slot")
+    counts, arr = _atex_counts(counts, T)
+    if slot.numel() != int(T):
+        raise PvdHipError("slot must hold T values")
+    Wt, Ht = mesh_atex_layout(counts)[:2]
+    if tuple(texture.shape) != (Ht, Wt, 3):
+        raise PvdHipError("texture must be [%d,%d,3] for counts=%s, got %s" % (Ht, Wt, counts, tuple(texture.shape)))
+    N = int(tri.numel())
+    if bary.numel() != 2 * N or color.numel() != 3 * N or bg3.numel() < 3:
+        raise PvdHipError("bary must hold 2 N, color 3 N and bg3 3 values")
+    _call("pvd_mesh_atex_sample", dev, _p(texture), _u32(T), arr, _p(slot), _p(tri), _p(bary), _u32(N), _p(bg3), _p(color))
 
 
 # --------------------------------------------------------------------------- view-dependent atlas (csrc/pvd_hip_mesh_shtex.h)

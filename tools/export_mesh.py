@@ -6,7 +6,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
   python tools/export_mesh.py student.pth --model-type vm -o student.ply [--resolution 256 --threshold T --resolution0 300]
                               [--min-component N] [--largest-only] [--normals] [--colors] [--simplify G [--simplify-report]]
                               [--smooth N [--smooth-lambda L --smooth-mu M] [--smooth-report]] [--render-check N]
-                              [--clean [--min-shell N] [--largest-shell-only]] [--topology-report] [--texture S [--texture-sh L]]
+                              [--clean [--min-shell N] [--largest-shell-only]] [--topology-report] [--texture S [--texture-sh L]] [--texture-density D]
                               [--cull-hidden {shells,triangles} [--exposure-dirs D --exposure-samples S] [--exposure-report]]
                               [--tsdf N [--tsdf-res HxW] [--tsdf-trunc K]]
 
@@ -49,6 +49,10 @@ normals are recomputed, the colours are taken and the --texture atlas is baked -
 texels and as many evaluations of the model.  (With it the colours are therefore those at the vertices of the final mesh.)
 --exposure-report prints one JSON line, cull_hidden's report: triangles and vertices before and after, hidden triangles, shells before
 and dropped, the ray totals; with --texture also atlas_before and atlas_after, [width, height] of the atlas without and with the cull.
+--texture-density D bakes onto an area-adaptive atlas instead (pvd/mesh.py: adaptive_atlas, csrc/mesh_atex.hip): every triangle gets the
+smallest cell edge of 4, 8, 16, 32, 64 texels that gives it D texels per unit length along its longest edge (--texture S, one of these, is
+then the largest cell edge allowed), and the triangles of one cell size share a band of the image.  It prints the triangles per cell size,
+how many were capped, the atlas size and its fill; .obj, .mtl, .png and --render-check work as with --texture.  Not with --texture-sh.
 --texture-sh L (1 .. 4, needs --texture S) bakes a view-dependent atlas instead (pvd/mesh.py: bake_sh_texture, csrc/mesh_shtex.hip): L * L
 spherical-harmonics coefficients per channel and texel, fitted to the model's colour along 64 directions.  The .png / .obj / .mtl are
 written from its view-independent part; the coefficients go to <stem>.shtex.npy ([height, width, L * L, 3] float32, numpy.save) with a
@@ -126,15 +130,25 @@ def render_check(model, m, views, res=200, textured=False, texture=None):
     return meter.report(), (float(diff) / n if n else float("nan")), n
 
 
+def _atlas_cell(m, texture, texture_density):
+    """What bake_texture takes as S: the integer cell edge, or with texture_density > 0 the adaptive atlas of the mesh in m (texture:
+    its largest cell edge where given, 64 otherwise)."""
+    if float(texture_density) > 0.0:
+        from pvd.mesh import adaptive_atlas
+        return adaptive_atlas(m["vertices"], m["triangles"], float(texture_density), max_cell=int(texture) if int(texture) > 0 else 64)
+    return int(texture)
+
+
 @torch.no_grad()
-def cull_surface(model, m, mode, n_dirs=64, samples=1, colors=False, texture=0, from_faces=False, texture_sh=0):
+def cull_surface(model, m, mode, n_dirs=64, samples=1, colors=False, texture=0, from_faces=False, texture_sh=0, texture_density=0.0):
     """--cull-hidden: extract_surface's dict m (taken WITHOUT colours and texture) goes through cull_hidden (pvd/mesh.py,
     csrc/mesh_expose.hip) with exposure_directions(n_dirs) and `samples` points per triangle; only then are the normals recomputed
     (from_faces: face_vertex_normals of what is left, for a smoothed mesh; otherwise the normals it has follow the selection), the
     colours taken (colors: vertex_colors at the vertices that are left) and the atlas baked (texture=S): hidden geometry costs neither
     model evaluations nor texels.  vertex_map and triangle_map, where m has them, are composed with cull_hidden's.  Returns
     cull_hidden's report, with mode, directions and samples, and with atlas_before / atlas_after = [width, height] where texture > 0.
-    texture_sh=L > 0: the atlas is bake_sh_texture's, under the keys extract_surface(texture_sh=L) uses."""
+    texture_sh=L > 0: the atlas is bake_sh_texture's, under the keys extract_surface(texture_sh=L) uses.  texture_density=D > 0: the
+    atlas is the adaptive one of what is left (atlas_after only)."""
     from pvd.mesh import bake_sh_texture, bake_texture, cull_hidden, exposure_directions, face_vertex_normals, texture_layout, vertex_colors
     T0 = int(m["triangles"].shape[0])
     done = cull_hidden(m["vertices"], m["triangles"], normals=m["normals"], mode=mode,
@@ -151,7 +165,12 @@ def cull_surface(model, m, mode, n_dirs=64, samples=1, colors=False, texture=0, 
         m["normals"] = face_vertex_normals(m["vertices"], m["triangles"])
     if colors:
         m["colors"] = vertex_colors(model, m["vertices"], m["normals"])
-    if int(texture) > 0:
+    if float(texture_density) > 0.0:
+        cell = _atlas_cell(m, texture, texture_density)
+        report["atlas_after"] = [cell["layout"]["width"], cell["layout"]["height"]]
+        baked = bake_texture(model, m["vertices"], m["triangles"], cell, normals=m["normals"])
+        m.update(texture=baked["texture"], uv=baked["uv"], texture_cell=cell)
+    elif int(texture) > 0:
         for key, T in (("atlas_before", T0), ("atlas_after", int(m["triangles"].shape[0]))):
             lay = texture_layout(T, int(texture))
             report[key] = [lay["width"], lay["height"]]
@@ -178,7 +197,7 @@ def load_view_data(root, split="train", downscale=1, device="cpu"):
 
 
 @torch.no_grad()
-def project_surface(model, m, n_views, size=400, best=False, colors=True, texture=0, min_opacity=0.5, views=None):
+def project_surface(model, m, n_views, size=400, best=False, colors=True, texture=0, min_opacity=0.5, views=None, texture_density=0.0):
     """--project-views N: the colours of extract_surface's dict m from what the model RENDERS, not from its colour head seen straight
     on: N tsdf_poses views of size x size are rendered (render_depth_maps: colour maps, and the opacity as the weight image, 0 below
     min_opacity) and projected onto the mesh (pvd/mesh.py: project_views, csrc/mesh_project.hip) -- the vertex colours (colors), and with
@@ -207,10 +226,11 @@ def project_surface(model, m, n_views, size=400, best=False, colors=True, textur
         out = project_views(m["vertices"], m["normals"], m["vertices"], m["triangles"], color, poses, intr, fallback=own, **kw)
         m["colors"], m["project_seen"] = out["colors"], out["seen"]
         report.update(vertices_seen=out["totals"]["seen"], vertices_unseen=out["totals"]["unseen"])
-    if int(texture) > 0:
+    if int(texture) > 0 or float(texture_density) > 0.0:  # (texture_density: the adaptive atlas, _atlas_cell)
+        cell = _atlas_cell(m, texture, texture_density)
         baked = bake_texture(view_source(m["vertices"], m["triangles"], color, poses, intr, fallback=own, **kw), m["vertices"],
-                             m["triangles"], int(texture), normals=m["normals"])
-        m.update(texture=baked["texture"], uv=baked["uv"], texture_cell=int(texture))
+                             m["triangles"], cell, normals=m["normals"])
+        m.update(texture=baked["texture"], uv=baked["uv"], texture_cell=cell)
     return report
 
 
@@ -247,6 +267,9 @@ def main(argv=None):
     ap.add_argument("--topology-report", action="store_true", help="print mesh_topology of the mesh about to be written as JSON")
     ap.add_argument("--texture", type=int, default=0, metavar="S",
                     help="bake a texture atlas with S x S texels per pair of triangles (4 .. 64) and write .obj, .mtl and .png next to the PLY")
+    ap.add_argument("--texture-density", type=float, default=0.0, metavar="D",
+                    help="bake onto an area-adaptive atlas instead: D texels per unit length, a cell edge of 4 .. 64 per triangle "
+                         "(--texture S, one of 4 8 16 32 64, caps it); writes .obj, .mtl and .png like --texture")
     ap.add_argument("--texture-sh", type=int, default=0, metavar="L",
                     help="with --texture S: bake L * L spherical-harmonics coefficients per texel (1 .. 4), the colour as a function of the view; "
                          "writes <stem>.shtex.npy and .shtex.json next to the .png, which holds the view-independent part")
@@ -276,7 +299,11 @@ def main(argv=None):
         ap.error("--project-best needs --project-views N or --project-data DIR")
     if a.project_data is None and (a.project_split != "train" or a.project_downscale != 1):
         ap.error("--project-split and --project-downscale need --project-data DIR")
-    if projecting and (a.texture_sh > 0 or a.cull_hidden or not (a.colors or a.texture > 0) or a.project_size < 2 or a.project_downscale < 1):
+    adaptive = a.texture_density > 0.0
+    textured = a.texture > 0 or adaptive
+    if not a.texture_density >= 0.0 or a.texture_density == float("inf") or (adaptive and (a.texture_sh > 0 or a.texture not in (0, 4, 8, 16, 32, 64))):
+        ap.error("--texture-density must be positive and finite, goes with --texture 4, 8, 16, 32 or 64 only, and not with --texture-sh")
+    if projecting and (a.texture_sh > 0 or a.cull_hidden or not (a.colors or textured) or a.project_size < 2 or a.project_downscale < 1):
         ap.error("projection needs --colors or --texture, a size of at least 2, and goes with neither --texture-sh nor --cull-hidden")
     if a.tsdf < 0:
         ap.error("--tsdf N: the number of views must not be negative")
@@ -292,7 +319,7 @@ def main(argv=None):
         ap.error("--min-shell and --largest-shell-only need --clean")
     if a.texture_sh != 0 and (a.texture <= 0 or not 1 <= a.texture_sh <= 4):
         ap.error("--texture-sh must be 1 .. 4 and needs --texture S")
-    if a.render_check > 0 and not (a.colors or a.texture > 0):
+    if a.render_check > 0 and not (a.colors or textured):
         ap.error("--render-check needs --colors or --texture")
     dev = torch.device("cuda:0")
     opt = PVDConfig(model_type=a.model_type, resolution0=a.resolution0, plenoxel_res=a.plenoxel_res)
@@ -306,7 +333,7 @@ def main(argv=None):
     kw = dict(resolution=a.resolution, threshold=thresh, min_points=a.min_component, largest_only=a.largest_only, smooth=a.smooth,
               smooth_lambda=a.smooth_lambda, smooth_mu=a.smooth_mu, clean=a.clean, min_shell_triangles=a.min_shell,
               largest_shell_only=a.largest_shell_only)
-    compare = a.texture > 0 and a.render_check > 0  # the three renders need the vertex colours too, written or not
+    compare = textured and a.render_check > 0  # the three renders need the vertex colours too, written or not
     surface = extract_surface
     if a.tsdf > 0:  # the same dict from fused depth maps: the level is 0 of -field, the TSDF being positive outside
         import math
@@ -323,11 +350,12 @@ def main(argv=None):
     if a.cull_hidden:  # the geometry first; normals for the colours' sake too; colours and texture after the cull
         m = surface(model, normals=a.normals or a.colors or compare, colors=False, simplify=a.simplify, **kw)
         exposure = cull_surface(model, m, a.cull_hidden, a.exposure_dirs, a.exposure_samples, colors=a.colors or compare, texture=a.texture,
-                                from_faces=a.smooth > 0, texture_sh=a.texture_sh)
+                                from_faces=a.smooth > 0, texture_sh=a.texture_sh, texture_density=a.texture_density)
     else:
         # (with a projection the colours and the atlas come from the views below: the model's own are not taken first)
         m = surface(model, normals=a.normals or projecting, colors=(a.colors or compare) and not projecting, simplify=a.simplify,
                     **(dict(texture=a.texture) if a.texture > 0 and not projecting else {}),
+                    **(dict(texture_density=a.texture_density) if adaptive and not projecting else {}),
                     **(dict(texture_sh=a.texture_sh) if a.texture_sh > 0 else {}), **kw)
     if projecting:  # the colours and the atlas from views projected onto the mesh; the model's own colour is only the fallback
         if m["normals"] is None:  # (a surface function that returned none)
@@ -335,7 +363,7 @@ def main(argv=None):
             m["normals"] = face_vertex_normals(m["vertices"], m["triangles"])
         views = None if a.project_data is None else load_view_data(a.project_data, a.project_split, a.project_downscale, dev)
         projected = project_surface(model, m, a.project_views, a.project_size, a.project_best, colors=a.colors or compare, texture=a.texture,
-                                    views=views)
+                                    views=views, texture_density=a.texture_density)
         print("projected %d views at %s (%s)%s: %s" % (projected["views"], projected["size"], projected["mode"],
                                                       "" if views is None else " from " + a.project_data,
                                                       json.dumps({k: v for k, v in projected.items() if k.startswith("vertices")})))
@@ -382,12 +410,20 @@ def main(argv=None):
     if a.topology_report:
         for top in ((m["topology"]["before"], m["topology"]["after"]) if a.clean else (mesh_topology(m["vertices"], m["triangles"]),)):
             print(json.dumps(top))
-    if a.texture > 0:
+    if textured:
         stem = os.path.splitext(out)[0]
         write_png(stem + ".png", m["texture_diffuse"] if a.texture_sh > 0 else m["texture"])
         write_obj(stem + ".obj", m["vertices"], m["triangles"], m["uv"], os.path.basename(stem + ".png"), normals=m["normals"] if a.normals else None)
-        print("%s.obj, .mtl, .png: texture %d x %d, %d x %d texels per pair of triangles"
-              % (stem, m["texture"].shape[1], m["texture"].shape[0], a.texture, a.texture))
+        if adaptive:
+            atlas = m["texture_cell"]
+            proper = sum(n * (c - 3) ** 2 for n, c in zip(atlas["counts"], atlas["layout"]["cell"])) / 2.0  # the triangles proper: m^2 / 2 each
+            print("%s.obj, .mtl, .png: adaptive texture %d x %d at %g texels per unit length; triangles per cell edge %s: %s, %d capped; fill %.1f %%"
+                  % (stem, m["texture"].shape[1], m["texture"].shape[0], a.texture_density, "/".join(str(c) for c in atlas["layout"]["cell"]),
+                     "/".join(str(n) for n in atlas["counts"]), atlas["capped"],
+                     100.0 * proper / (m["texture"].shape[0] * m["texture"].shape[1])))
+        else:
+            print("%s.obj, .mtl, .png: texture %d x %d, %d x %d texels per pair of triangles"
+                  % (stem, m["texture"].shape[1], m["texture"].shape[0], a.texture, a.texture))
         if a.texture_sh > 0:
             np.save(stem + ".shtex.npy", m["texture"].cpu().numpy())
             with open(stem + ".shtex.json", "w") as f:
