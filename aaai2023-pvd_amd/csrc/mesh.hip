@@ -18,6 +18,7 @@
 // The count -> one-workgroup scan -> offsets shape of csrc/block_scan.h: no workgroup waits on another one of the same launch,
 // nothing is atomic, and the output does not depend on the order in which workgroups run.
 #include "block_scan.h"
+#include "mesh_gradient.h"
 
 #include "../../include/pvd_hip_mesh.h"
 #include "../../include/pvd_hip_mesh_attr.h"
@@ -226,24 +227,6 @@ __global__ __launch_bounds__(kThreads) void k_mesh_emit(const float *__restrict_
             const bool flip = (odd ^ (A & 1u) ^ (cnt == 3 ? 1u : 0u)) != 0;
             put(edge(A, B), edge(A, C), edge(A, D), flip);
         }
-    }
-}
-
-// world gradient of u at the lattice point q = (c[0], c[1], c[2]) (include/pvd_hip_mesh_attr.h): central differences inside the
-// lattice, one-sided ones on its faces, each scaled by the axis' lattice points per world unit
-__device__ __forceinline__ void world_gradient(const float *__restrict__ u, uint32_t R, uint32_t q, const uint32_t c[3], const float inv_h[3],
-                                               float g[3]) {
-    const uint32_t stride[3] = {R * R, R, 1u};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float d;
-        if (c[a] == 0)
-            d = u[q + stride[a]] - u[q];
-        else if (c[a] == R - 1)
-            d = u[q] - u[q - stride[a]];
-        else
-            d = (u[q + stride[a]] - u[q - stride[a]]) * 0.5f;
-        g[a] = d * inv_h[a];
     }
 }
 

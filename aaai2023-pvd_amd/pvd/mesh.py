@@ -3,7 +3,9 @@
 reference: extract_fields / extract_geometry, distill_mutual/utils.py:442-488 -- a density volume of resolution^3 samples filled
 chunk by chunk through the host, mcubes.marching_cubes on the host, vertices mapped back into the box.  Here the volume is filled
 on the device and the surface is extracted by the kernels of csrc/mesh.hip (include/pvd_hip_mesh.h: marching tetrahedra on the
-Kuhn split; shared vertices, watertight, deterministic order); the two totals are the only values read back.
+Kuhn split; shared vertices, watertight, deterministic order); the two totals are the only values read back.  method="nets" takes
+the kernels of csrc/mesh_nets.hip instead (csrc/pvd_hip_mesh_nets.h: naive surface nets, one vertex per active cell, two triangles per
+crossing lattice edge -- fewer and better-shaped triangles, not manifold at ambiguous faces, open where it leaves the box).
 
 The reference's meshes carry the density "floaters" of the field as small closed shells (network.py:601: "lots of noisy outliers
 in hashnerf"); label_components / drop_components (csrc/components.hip, include/pvd_hip_components.h) take them out of the volume
@@ -41,28 +43,43 @@ def density_field(query, R, bmin, bmax, chunk=1 << 21, device=None):
     return u
 
 
-def extract_mesh(field, thresh, bmin, bmax, with_normals=False):
+MESH_METHODS = ("tetrahedra", "nets")
+
+
+def extract_mesh(field, thresh, bmin, bmax, with_normals=False, method="tetrahedra"):
     """(vertices [V,3] f32, triangles [T,3] int32), device tensors, of the surface field = thresh (inside: field > thresh; normals
     point outwards); field [R,R,R] f32 on the device, vertices in the box bmin .. bmax.  One read-back: the two totals.
     with_normals=True: (vertices, triangles, normals [V,3] f32) -- the outward unit normal of every vertex from the gradient of the
-    field (include/pvd_hip_mesh_attr.h), one more launch on the same workspace; (0,0,0) where the gradient is zero or not finite."""
+    field (include/pvd_hip_mesh_attr.h), one more launch on the same workspace; (0,0,0) where the gradient is zero or not finite.
+    method="tetrahedra" (the default): marching tetrahedra on the Kuhn split (include/pvd_hip_mesh.h), watertight, vertices on lattice
+    edges.  method="nets": naive surface nets (csrc/pvd_hip_mesh_nets.h) -- one vertex per active cell at the mean of its edge
+    crossings, two triangles per crossing interior lattice edge; no slivers by construction and a fraction of the triangles, but four
+    quads meet in one edge at an ambiguous lattice face (not manifold there), and the surface is open where it leaves the box.
+    Anything else: ValueError."""
     import pvd_hip
+    if method not in MESH_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (MESH_METHODS, method))
     if field.dim() != 3 or field.shape[0] != field.shape[1] or field.shape[0] != field.shape[2]:
         raise ValueError("field must be [R,R,R]")
     field = field.contiguous()
     R, dev = int(field.shape[0]), field.device
     lo, hi = _box(bmin, bmax, dev)
-    ws = torch.empty(pvd_hip.mesh_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    if method == "nets":
+        workspace_bytes, count, emit, emit_normals = (pvd_hip.mesh_nets_workspace_bytes, pvd_hip.mesh_nets_count, pvd_hip.mesh_nets_emit,
+                                                      pvd_hip.mesh_nets_normals)
+    else:
+        workspace_bytes, count, emit, emit_normals = pvd_hip.mesh_workspace_bytes, pvd_hip.mesh_count, pvd_hip.mesh_emit, pvd_hip.mesh_normals
+    ws = torch.empty(workspace_bytes(R), dtype=torch.uint8, device=dev)
     totals = torch.zeros(2, dtype=torch.int32, device=dev)
-    pvd_hip.mesh_count(field, R, float(thresh), ws, totals)
+    count(field, R, float(thresh), ws, totals)
     V, T = (int(v) for v in totals.tolist())
     vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
     triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
-    pvd_hip.mesh_emit(field, R, float(thresh), lo, hi, ws, vertices, triangles)
+    emit(field, R, float(thresh), lo, hi, ws, vertices, triangles)
     if not with_normals:
         return vertices, triangles
     normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    pvd_hip.mesh_normals(field, R, float(thresh), lo, hi, ws, normals)
+    emit_normals(field, R, float(thresh), lo, hi, ws, normals)
     return vertices, triangles, normals
 
 
@@ -76,7 +93,9 @@ def label_components(field, thresh):
     """(labels [R,R,R] int32, sizes [R,R,R] int32, stats) of the connected components of the set field > thresh, under the
     connectivity of the mesher's Kuhn split (14 neighbours).  labels: the smallest linear index of the point's component, -1
     outside; sizes: the component's number of points at its label, 0 elsewhere; both stay on the device.  stats, the one
-    read-back: (components, inside points, size of the largest component, its label) as Python ints."""
+    read-back: (components, inside points, size of the largest component, its label) as Python ints.
+    The components follow the Kuhn split's connectivity whatever mesher is used afterwards: with extract_mesh(method="nets") the
+    shells of the mesh can differ from them at ambiguous lattice faces."""
     import pvd_hip
     field, R = _cube(field)
     labels = torch.empty(R, R, R, dtype=torch.int32, device=field.device)
@@ -103,7 +122,9 @@ def drop_components(field, thresh, min_points=0, largest_only=False):
     """(field', kept): field with every point of a dropped component set to thresh, i.e. moved outside -- dropped are the components
     of fewer than min_points points and, with largest_only, all but the largest one (ties: the one with the smaller label).  The
     mesh of field' is the mesh of field without the shells of the dropped components, vertex bits included.  field is not changed.
-    kept, the one read-back: (components kept, points kept)."""
+    kept, the one read-back: (components kept, points kept).
+    The components follow the Kuhn split's connectivity: with extract_mesh(method="nets") a dropped component's shell can differ from
+    the shells of the mesh at ambiguous lattice faces (two components that touch across a face diagonal share a nets edge)."""
     field, R = _cube(field)
     out = torch.empty_like(field)
     _, kept = _drop(field, R, thresh, min_points, largest_only, out)
@@ -123,12 +144,14 @@ def default_threshold(model):
 
 
 def extract_geometry(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, return_field=False, min_points=0,
-                     largest_only=False, return_counts=False):
+                     largest_only=False, return_counts=False, method="tetrahedra"):
     """reference: extract_geometry, utils.py:473-488, with the density of `model` as the query.  The box defaults to
     model.aabb_infer, the threshold to default_threshold(model).  Returns (vertices, triangles) on the device (and the density
     volume with return_field=True).  min_points > 0 or largest_only: the volume is filtered in place by drop_components' rule
     between the two steps (the returned volume is the filtered one); return_counts=True then appends (components found,
-    components kept, points kept), None where nothing was filtered."""
+    components kept, points kept), None where nothing was filtered.  method: extract_mesh's mesher, "tetrahedra" or "nets"."""
+    if method not in MESH_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (MESH_METHODS, method))
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -140,7 +163,7 @@ def extract_geometry(model, resolution=256, threshold=None, bmin=None, bmax=None
         stats, kept = _drop(u, int(resolution), threshold, min_points, largest_only, u)
         if return_counts:
             counts = (int(stats[0]),) + tuple(int(v) for v in kept.tolist())
-    vertices, triangles = extract_mesh(u, threshold, lo, hi)
+    vertices, triangles = extract_mesh(u, threshold, lo, hi, method=method)
     result = (vertices, triangles, u) if return_field else (vertices, triangles)
     return result + (counts,) if return_counts else result
 
@@ -172,7 +195,7 @@ def vertex_colors(model, vertices, normals, chunk=1 << 20, autocast=True):
 
 def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None, chunk=1 << 21, min_points=0, largest_only=False,
                     normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, clean=False,
-                    min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0, texture_density=0.0):
+                    min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0, texture_density=0.0, method="tetrahedra"):
     """extract_geometry with what a viewer needs next to the geometry, as a dict: vertices, triangles, normals (extract_mesh's
     with_normals) and colors (vertex_colors), None where not asked for; field (the density volume, filtered where min_points > 0
     or largest_only), threshold, and counts = (components found, components kept, points kept), None where nothing was filtered.
@@ -195,7 +218,12 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
     view-independent part, next to uv and texture_cell.  texture_sh=0: the dict is what it was.
     texture_density=D > 0: the flat bake goes onto an area-adaptive atlas (adaptive_atlas: D texels per unit length, a cell edge per
     triangle, at most texture=S where given and 64 otherwise); texture_cell is then that atlas.  With texture_sh it raises ValueError.
-    texture_density=0: the dict is what it was."""
+    texture_density=0: the dict is what it was.
+    method="nets": the geometry and the normals come from the surface nets mesher (extract_mesh's method); everything after it takes
+    (vertices, triangles) and works on them unchanged.  min_points / largest_only still filter by the Kuhn split's components.
+    method="tetrahedra": the dict is what it was."""
+    if method not in MESH_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (MESH_METHODS, method))
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -208,11 +236,11 @@ def extract_surface(model, resolution=256, threshold=None, bmin=None, bmax=None,
         counts = (int(stats[0]),) + tuple(int(v) for v in kept.tolist())
     nrm = col = None
     if normals or colors:
-        vertices, triangles, nrm = extract_mesh(u, threshold, lo, hi, with_normals=True)
+        vertices, triangles, nrm = extract_mesh(u, threshold, lo, hi, with_normals=True, method=method)
         if colors:
             col = vertex_colors(model, vertices, nrm)
     else:
-        vertices, triangles = extract_mesh(u, threshold, lo, hi)
+        vertices, triangles = extract_mesh(u, threshold, lo, hi, method=method)
     return _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, dict(field=u, threshold=float(threshold), counts=counts),
                            smooth, smooth_lambda, smooth_mu, simplify, clean, min_shell_triangles, largest_shell_only, texture, texture_sh, texture_density)
 
@@ -1572,7 +1600,8 @@ def render_depth_maps(model, poses, intrinsics, H, W, min_opacity=0.5, free_opac
 def extract_surface_tsdf(model, poses=None, intrinsics=None, H=400, W=400, resolution=256, tau=None, bmin=None, bmax=None,
                          views_per_batch=8, min_weight=1.0, unknown=-1.0, min_opacity=0.5, free_opacity=0.05, min_points=0,
                          largest_only=False, normals=True, colors=True, simplify=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53,
-                         clean=False, min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0, texture_density=0.0):
+                         clean=False, min_shell_triangles=0, largest_shell_only=False, texture=0, texture_sh=0, texture_density=0.0,
+                         method="tetrahedra"):
     """extract_surface with the geometry taken from what the model RENDERS: depth and colour maps of `poses` (render_depth_maps;
     default tsdf_poses(), with intrinsics of a 50 degree field of view where none are given) are fused into a TSDFVolume over the box
     (default model.aabb_infer), views_per_batch at a time, and the zero level of tsdf_field is meshed -- where the model's rays end,
@@ -1580,8 +1609,10 @@ def extract_surface_tsdf(model, poses=None, intrinsics=None, H=400, W=400, resol
     vertices, triangles, normals (the gradient of the fused field: extract_mesh's with_normals), colors (tsdf_vertex_colors: the
     fused colours, no second pass over the model), field (the TSDF, positive outside), threshold = 0.0 and counts, plus tsdf_totals
     (tsdf_field's) and views.  min_points, largest_only, smooth, simplify, clean, texture and texture_sh mean exactly what they mean in
-    extract_surface and go through the same functions, and so does texture_density."""
+    extract_surface and go through the same functions, and so do texture_density and method (the mesher of the zero level)."""
     import math
+    if method not in MESH_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (MESH_METHODS, method))
     aabb = model.aabb_infer
     lo = aabb[:3] if bmin is None else bmin
     hi = aabb[3:] if bmax is None else bmax
@@ -1608,11 +1639,11 @@ def extract_surface_tsdf(model, poses=None, intrinsics=None, H=400, W=400, resol
         field = -u
     nrm = col = None
     if normals or colors:
-        vertices, triangles, nrm = extract_mesh(u, 0.0, lo, hi, with_normals=True)
+        vertices, triangles, nrm = extract_mesh(u, 0.0, lo, hi, with_normals=True, method=method)
         if colors:
             col = tsdf_vertex_colors(acc, vertices, min_weight=min_weight)
     else:
-        vertices, triangles = extract_mesh(u, 0.0, lo, hi)
+        vertices, triangles = extract_mesh(u, 0.0, lo, hi, method=method)
     extra = dict(field=field, threshold=0.0, counts=counts, tsdf_totals=totals, views=acc.views)
     return _finish_surface(model, vertices, triangles, nrm, col, normals, lo, hi, extra, smooth, smooth_lambda, smooth_mu, simplify, clean,
                            min_shell_triangles, largest_shell_only, texture, texture_sh, texture_density)

@@ -129,6 +129,8 @@ ENTRY_POINTS_MESH_PROJECT = ("pvd_mesh_project_integrate", "pvd_mesh_project_fin
 # ... and the area-adaptive texture atlas of csrc/pvd_hip_mesh_atex.h (tests/test_abi_mesh_atex.py)
 ENTRY_POINTS_MESH_ATEX = ("pvd_mesh_atex_workspace_bytes", "pvd_mesh_atex_build", "pvd_mesh_atex_layout", "pvd_mesh_atex_points",
                           "pvd_mesh_atex_sample")
+# ... and the surface nets mesher of csrc/pvd_hip_mesh_nets.h (tests/test_abi_mesh_nets.py)
+ENTRY_POINTS_MESH_NETS = ("pvd_mesh_nets_workspace_bytes", "pvd_mesh_nets_count", "pvd_mesh_nets_emit", "pvd_mesh_nets_normals")
 # ... and the prefix of a group of G steps in one launch per stage, include/pvd_hip_prefix.h (tests/test_abi_prefix.py)
 ENTRY_POINTS_PREFIX = ("pvd_make_ray_batch_group", "pvd_march_group_workspace_bytes", "pvd_march_rays_train_group",
                        "pvd_composite_rays_train_bg_forward_group")
@@ -136,7 +138,7 @@ for _name in (ENTRY_POINTS + ENTRY_POINTS_MLP + ENTRY_POINTS_METRICS + ENTRY_POI
               + ENTRY_POINTS_COMPONENTS + ENTRY_POINTS_MESH_ATTR + ENTRY_POINTS_MESH_DIST + ENTRY_POINTS_MESH_SIMPLIFY + ENTRY_POINTS_MESH_RAY
               + ENTRY_POINTS_MESH_SMOOTH + ENTRY_POINTS_MESH_TOPO + ENTRY_POINTS_MESH_WINDING + ENTRY_POINTS_MESH_TEX
               + ENTRY_POINTS_MESH_EXPOSE + ENTRY_POINTS_MESH_SHTEX + ENTRY_POINTS_MESH_TSDF + ENTRY_POINTS_MESH_PROJECT
-              + ENTRY_POINTS_MESH_ATEX):
+              + ENTRY_POINTS_MESH_ATEX + ENTRY_POINTS_MESH_NETS):
     if _name not in ("pvd_status_string", "pvd_last_hip_error"):
         getattr(_lib, _name).restype = ctypes.c_int
 # (an A/B library built before include/pvd_hip_prefix.h existed still loads through PVD_HIP_LIB: it runs every per-step schedule, and a
@@ -155,6 +157,7 @@ _lib.pvd_mesh_smooth_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_topo_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_winding_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_mesh_atex_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvd_mesh_nets_workspace_bytes.restype = ctypes.c_size_t
 _lib.pvd_composite_objective_blocks.restype = ctypes.c_uint32
 _lib.pvd_composite_objective_blocks_fixed.restype = ctypes.c_uint32
 
@@ -1686,6 +1689,68 @@ def mesh_normals(field, R, thresh, bmin, bmax, workspace, normals):
         raise PvdHipError("normals must be [V,3]")
     _call("pvd_mesh_normals", dev, _p(field), _u32(R), _f32(thresh), _p(bmin), _p(bmax), _p(workspace), ctypes.c_size_t(workspace.numel()),
           _p(normals), _u32(normals.numel() // 3))
+
+
+# --------------------------------------------------------------------------- surface nets (csrc/pvd_hip_mesh_nets.h)
+def mesh_nets_workspace_bytes(R):
+    """pvd_mesh_nets_workspace_bytes: bytes of workspace mesh_nets_count / _emit / _normals need for a field of R^3 samples."""
+    n = int(_lib.pvd_mesh_nets_workspace_bytes(_u32(R))) if 0 <= int(R) < 2 ** 32 else 0
+    if n == 0:
+        raise PvdHipError("pvd_mesh_nets_workspace_bytes: R must be 2 .. %d, got %d" % (MESH_MAX_R, int(R)))
+    return n
+
+
+def _mesh_nets_common(field, R, workspace):
+    _want(field, torch.float32, "field"), _want(workspace, torch.uint8, "workspace")
+    R = int(R)
+    if field.numel() != R ** 3:
+        raise PvdHipError("field must hold R^3 floats")
+    if workspace.numel() < mesh_nets_workspace_bytes(R):
+        raise PvdHipError("workspace too small: mesh_nets_workspace_bytes(R) bytes are needed")
+    return R
+
+
+def mesh_nets_count(field, R, thresh, workspace, totals):
+    """pvd_mesh_nets_count: the count pass and the two scans of the surface nets of field > thresh (field [R,R,R] f32, x-major); leaves
+    the workspace (uint8, mesh_nets_workspace_bytes(R)) as mesh_nets_emit needs it; totals int32 [2] <- (vertices, triangles), on the
+    device."""
+    dev = _dev(field, workspace, totals)
+    R = _mesh_nets_common(field, R, workspace)
+    _want(totals, torch.int32, "totals")
+    if totals.numel() < 2:
+        raise PvdHipError("totals must hold 2 int32 values")
+    _call("pvd_mesh_nets_count", dev, _p(field), _u32(R), _f32(thresh), _p(workspace), ctypes.c_size_t(workspace.numel()), _p(totals))
+
+
+def mesh_nets_emit(field, R, thresh, bmin, bmax, workspace, vertices, triangles):
+    """pvd_mesh_nets_emit: vertices [V,3] f32 (one per active cell, in the box bmin .. bmax, device f32 [3] each) and triangles [T,3] int32
+    (two per crossing interior lattice edge) of the SAME field, R, thresh and the workspace mesh_nets_count left; V and T are the totals
+    it wrote (both 0: nothing is launched)."""
+    dev = _dev(field, workspace, bmin, bmax, vertices, triangles)
+    R = _mesh_nets_common(field, R, workspace)
+    _f32_all(bmin=bmin, bmax=bmax, vertices=vertices)
+    _want(triangles, torch.int32, "triangles")
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    if vertices.numel() % 3 or triangles.numel() % 3:
+        raise PvdHipError("vertices must be [V,3] and triangles [T,3]")
+    V, T = vertices.numel() // 3, triangles.numel() // 3
+    _call("pvd_mesh_nets_emit", dev, _p(field), _u32(R), _f32(thresh), _p(bmin), _p(bmax), _p(workspace), ctypes.c_size_t(workspace.numel()),
+          _p(vertices), _u32(V), _p(triangles), _u32(T))
+
+
+def mesh_nets_normals(field, R, thresh, bmin, bmax, workspace, normals):
+    """pvd_mesh_nets_normals: normals [V,3] f32 <- the outward unit normal of every vertex mesh_nets_emit writes, the mean of the field's
+    gradient over the cell's edge crossings (R, thresh, box and workspace as for mesh_nets_emit); V == 0: nothing is launched."""
+    dev = _dev(field, workspace, bmin, bmax, normals)
+    R = _mesh_nets_common(field, R, workspace)
+    _f32_all(bmin=bmin, bmax=bmax, normals=normals)
+    if bmin.numel() < 3 or bmax.numel() < 3:
+        raise PvdHipError("bmin / bmax must hold 3 floats")
+    if normals.numel() % 3:
+        raise PvdHipError("normals must be [V,3]")
+    _call("pvd_mesh_nets_normals", dev, _p(field), _u32(R), _f32(thresh), _p(bmin), _p(bmax), _p(workspace),
+          ctypes.c_size_t(workspace.numel()), _p(normals), _u32(normals.numel() // 3))
 
 
 raymarching_backend = types.SimpleNamespace(

@@ -8,7 +8,7 @@ the device (pvd/mesh.py, csrc/mesh.hip), written as a binary PLY.
                               [--smooth N [--smooth-lambda L --smooth-mu M] [--smooth-report]] [--render-check N]
                               [--clean [--min-shell N] [--largest-shell-only]] [--topology-report] [--texture S [--texture-sh L]] [--texture-density D]
                               [--cull-hidden {shells,triangles} [--exposure-dirs D --exposure-samples S] [--exposure-report]]
-                              [--tsdf N [--tsdf-res HxW] [--tsdf-trunc K]]
+                              [--tsdf N [--tsdf-res HxW] [--tsdf-trunc K]] [--mesher {tetrahedra,nets}]
 
 The checkpoint is the reference's format (pvd/checkpoint.py); --model-type and the size flags must describe the model that wrote it.
 The threshold defaults to min(density_thresh, mean_density) of the loaded model (density_thresh where the file carries no mean).
@@ -73,7 +73,11 @@ test (pvd/mesh.py: project_views; csrc/mesh_project.hip), blended by cos^2 times
 best view; the model's colour head seen straight on is only the fallback where no view sees a point.  --render-check reports its usual
 lines, so the two bakes can be compared.  (With --simplify the third line's full-resolution mesh keeps the colour head's colours.)
 --project-data DIR [--project-split train] [--project-downscale K] projects the photographs of a Blender-format scene with their own
-poses (pvd.provider.BlenderScene) instead of renders; an alpha channel is the weight image."""
+poses (pvd.provider.BlenderScene) instead of renders; an alpha channel is the weight image.
+--mesher nets extracts the surface with naive surface nets (pvd/mesh.py: extract_mesh(method="nets"), csrc/mesh_nets.hip: one vertex per
+active cell, two triangles per crossing lattice edge -- a fraction of the triangles and no slivers, but not manifold at ambiguous lattice
+faces and open where the surface leaves the box) instead of marching tetrahedra, the default.  Every other flag works on the result;
+--min-component and --largest-only still follow the tetrahedra's connectivity."""
 import argparse
 import json
 import os
@@ -289,6 +293,8 @@ def main(argv=None):
                     help="project the photographs of a Blender-format scene (transforms_<split>.json, read through pvd.provider) instead of renders")
     ap.add_argument("--project-split", default="train", help="with --project-data: train, val, test, trainval or all")
     ap.add_argument("--project-downscale", type=int, default=1, metavar="K", help="with --project-data: read the photographs at 1 / K of their size")
+    ap.add_argument("--mesher", default="tetrahedra", choices=["tetrahedra", "nets"],
+                    help="marching tetrahedra (watertight, vertices on lattice edges) or naive surface nets (one vertex per cell, fewer triangles)")
     a = ap.parse_args(argv)
     projecting = a.project_views > 0 or a.project_data is not None
     if a.project_views < 0 or (a.project_views > 0 and a.project_data is not None):
@@ -332,7 +338,7 @@ def main(argv=None):
     filtering = a.min_component > 0 or a.largest_only
     kw = dict(resolution=a.resolution, threshold=thresh, min_points=a.min_component, largest_only=a.largest_only, smooth=a.smooth,
               smooth_lambda=a.smooth_lambda, smooth_mu=a.smooth_mu, clean=a.clean, min_shell_triangles=a.min_shell,
-              largest_shell_only=a.largest_shell_only)
+              largest_shell_only=a.largest_shell_only, **(dict(method=a.mesher) if a.mesher != "tetrahedra" else {}))
     compare = textured and a.render_check > 0  # the three renders need the vertex colours too, written or not
     surface = extract_surface
     if a.tsdf > 0:  # the same dict from fused depth maps: the level is 0 of -field, the TSDF being positive outside
@@ -372,6 +378,8 @@ def main(argv=None):
     carries = "positions" + (", normals" if a.normals else "") + (", colours" if a.colors else "")
     print("%s: %d vertices (%s), %d triangles at density %.6g, resolution %d"
           % (out, m["vertices"].shape[0], carries, m["triangles"].shape[0], thresh, a.resolution))
+    if a.mesher == "nets":
+        print("mesher: surface nets (one vertex per active cell; open where the surface leaves the box)")
     if a.tsdf > 0:
         print("tsdf: %d views at %s, truncation %g spacings; voxels %s" % (m["views"], a.tsdf_res, a.tsdf_trunc, json.dumps(m["tsdf_totals"])))
     if filtering:
@@ -380,7 +388,7 @@ def main(argv=None):
         print("smooth: %d iterations, lambda %g, mu %g" % (a.smooth, a.smooth_lambda, a.smooth_mu))
         if a.smooth_report:
             aabb = model.aabb_infer
-            raw_v, raw_t = extract_mesh(m["field"], thresh, aabb[:3], aabb[3:])
+            raw_v, raw_t = extract_mesh(m["field"], thresh, aabb[:3], aabb[3:], method=a.mesher)
             new_v = smooth_mesh(raw_v, raw_t, iterations=a.smooth, lam=a.smooth_lambda, mu=a.smooth_mu, bmin=aabb[:3], bmax=aabb[3:])
             spacing = float((aabb[3:] - aabb[:3]).double().max()) / (a.resolution - 1)
             d = compare_meshes(raw_v, raw_t, new_v, raw_t, tau=spacing)
@@ -392,7 +400,7 @@ def main(argv=None):
               % (a.simplify, m["full_counts"][0], m["vertices"].shape[0], m["full_counts"][1], m["triangles"].shape[0]))
         if a.simplify_report:
             aabb = model.aabb_infer
-            full_v, full_t = extract_mesh(m["field"], thresh, aabb[:3], aabb[3:])
+            full_v, full_t = extract_mesh(m["field"], thresh, aabb[:3], aabb[3:], method=a.mesher)
             diagonal = float((aabb[3:] - aabb[:3]).double().norm()) / a.simplify
             d = compare_meshes(full_v, full_t, m["vertices"], m["triangles"], tau=diagonal)
             print("simplified against original: hausdorff %.6g, chamfer %.6g, cell diagonal %.6g" % (d["hausdorff"], d["chamfer"], diagonal))
